@@ -26,6 +26,14 @@ launch  python bench.py --gpus N            spawns its N ranks itself (one proce
         ranks on GPU 0 over gloo (the world-size-2 test on a one-GPU box).
         Inputs are resident in HBM before the timed region; tables / precomputation are excluded exactly as
         benches/fft.rs:22-30 and src/bin/msms.rs:25,54-58 exclude them.
+modes   a plain run sets up, warms up (--warmup), times exactly --steps steps and prints the ONE JSON line (metric, value, unit,
+        higher_is_better, dtype, ms_per_step = milliseconds per timed step, config).  --full adds everything else: the same steps again
+        with per-kernel HIP events (ms_per_step_profiled, rooflines against ceilings measured in the process), the component loops, the
+        self-checks, the CPU baseline (the oracle), the GPU's identity and, N > 1, the strong-scaling section.
+        --dump-outputs DIR  writes what the last timed step handed its caller as DIR/<name>.npy (float64, one 32-bit half-limb per
+        value, low half first; an output of more than 2^17 rows as one fixed seeded sample of its rows, at most 64 MB in all):
+        ntt_out, msm_xy (affine x | y), msm_is_zero; --workload quotient: vanishing_points.  The inputs are seeded: the same arguments
+        give the same inputs in every run.
 value   whole-job units per second, 1 unit = 1 NTT element or 1 MSM scalar-point pair; the components are reported
         separately in "components" as NTT Melems/s and MSM Mpairs/s - those are the numbers BASELINE.md tracks.
 code    this file is the command line; the work is in benchlib/: headline.py (the timed region, checks, rooflines, the JSON line),
@@ -46,6 +54,8 @@ from benchlib.multi import single_process_child  # noqa: E402,F401  (tests/ call
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
+    if args.dump_outputs and (args.single_process or args.workload == "crossover"):
+        raise SystemExit("--dump-outputs: --single-process and --workload crossover have no device outputs to write")
     if args.single_process:
         from benchlib.multi import run_single_process
         return run_single_process(args)

@@ -149,6 +149,34 @@ def gpu_identity(torch, index):
 
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 17
+DUMP_SAMPLE_SEED = 0xD0_0A7
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every (name, array) as <path>/<name>.npy in float64.  A uint64 limb array becomes its 32-bit halves, low half
+    first ((rows, L) -> (rows, 2L)): every value is an integer below 2^32, which float64 holds exactly.  An array of more than
+    DUMP_SAMPLE_ROWS rows is written as the rows of one fixed seeded sample (sorted indices, the same in every run and every build).
+    Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total, shapes = 0, {}
+    for name, a in arrays:
+        a = np.ascontiguousarray(a)
+        if a.ndim and a.shape[0] > DUMP_SAMPLE_ROWS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            a = np.ascontiguousarray(a[idx])
+        if a.dtype.itemsize == 8:
+            a = a.view(np.uint64).view(np.uint32)
+        out = a.astype(np.float64)
+        total += out.nbytes
+        assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+        np.save(os.path.join(path, name + ".npy"), out)
+        shapes[name] = list(out.shape)
+    return shapes
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -162,6 +190,12 @@ def parse_args(argv=None):
     ap.add_argument("--same-device", action="store_true", help="all ranks on GPU 0, gloo backend (world-size-2 test on a one-GPU box)")
     ap.add_argument("--no-parts", action="store_true", help="strong scaling: a rank's share of a sharded vector as a zero-padded full-length vector (round-3 start) instead of its base range")
     ap.add_argument("--bucket-shard", action="store_true", help="strong scaling: a sharded vector is shared by BUCKET range (every rank reads the whole vector and keeps its N-th of the coarse bins) instead of by base range")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the profiled re-run and rooflines, the component loops, the self-checks, the CPU "
+                         "baseline, the GPU's identity and (N > 1) the strong-scaling section; a plain run only sets up, warms up, times --steps steps "
+                         "and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float64, one 32-bit half-limb per value)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--timed-only", action="store_true", help="run only the warm-up + timed region (for rocprofv3 --pmc passes)")

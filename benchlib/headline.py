@@ -1,13 +1,14 @@
 """benchlib.headline -- the default line of bench.py: K steps of (one forward 2^20 NTT + one 2^20-pair MSM) per GPU between two
-synchronisations, then the same steps with per-kernel HIP events for the rooflines, the component loops, the self-checks, the
-multi-GPU section and the ONE JSON line."""
+synchronisations and the ONE JSON line; with --full also the same steps with per-kernel HIP events for the rooflines, the component
+loops, the self-checks and the multi-GPU section."""
 import json
 import os
 import time
 from types import SimpleNamespace
 
 from . import components, multi
-from .common import (CURVES, HBM_PEAK_GBS, METRIC, SEED_MSM, SEED_NTT, STAGES, Ceilings, gpu_identity, kernel_source_hash, latest_profile)
+from .common import (CURVES, HBM_PEAK_GBS, METRIC, SEED_MSM, SEED_NTT, STAGES, Ceilings, dump_outputs, gpu_identity, kernel_source_hash,
+                     latest_profile)
 from .cpu import cpu_baseline
 from .quotient import run_quotient
 
@@ -110,7 +111,7 @@ def run(args):
                 dev.msm_execute_dev(pre, s, oxy, oz)
             if exchange:
                 ex.gather()
-                ex.combine()
+                ex.combine()   # into ex.sum_xy / ex.sum_zero
 
     def sync():
         torch.cuda.synchronize()
@@ -133,6 +134,55 @@ def run(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if gloo else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # ---- what the last timed step handed its caller: the transform and the MSM results (after the exchange: the global ones) ----
+    if args.dump_outputs and rank == 0:
+        outs = []
+        if do_ntt:
+            outs.append(("ntt_out", dev.to_host(y)))
+        if do_msm:
+            rxy, rz = (ex.sum_xy, ex.sum_zero) if exchange else (oxy, oz)
+            outs += [("msm_xy", dev.to_host(rxy).reshape(-1, 2 * cv["limbs"])), ("msm_is_zero", rz.cpu().numpy())]
+        dump_outputs(args.dump_outputs, outs)
+
+    units_per_step = (n if do_ntt else 0) + (((plan.pairs_local() if args.emulate_rank else batch * n)) if do_msm else 0)
+    value = (1 if strong else world) * units_per_step * args.steps / elapsed / 1e6
+    wl = {"both": "2^%d %s forward NTT + 2^%d-pair %s MSM per GPU per step" % (args.log_n, "TweedledeeBase" if args.curve == "tweedledee" else "Bls12377Scalar", args.log_n, args.curve),
+          "ntt": "2^%d forward NTT per GPU per step" % args.log_n,
+          "msm": ("ONE 2^%d-pair %s MSM per step, generators sharded by base range over the GPUs" if strong else "2^%d-pair %s MSM per GPU per step") % (args.log_n, args.curve),
+          "commit9": "9-wire commitment batch: nine 2^%d-pair %s MSMs against the same generators per step (generators sharded by base range over the GPUs)" % (args.log_n, args.curve)}[args.workload]
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "M units/s (1 unit = 1 NTT element or 1 MSM scalar-point pair; components below)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+        "dtype": "u32", "data": "synthetic",
+        "config": {"workload": wl, "log_n": args.log_n, "curve": args.curve,
+                   "sharding": ("whole vectors per rank, the remainder sharded by base range; one packed all-gather + device point sum" if strong else
+                                "independent NTTs; MSM sharded by base range + one packed all-gather of partial points + device point sum") if world > 1 else "single GPU",
+                   "backend": ("gloo (ranks share GPU 0)" if gloo else "nccl (RCCL)") if world > 1 else None,
+                   "seeds": {"ntt": SEED_NTT, "msm": SEED_MSM}, "kernel_source_sha": kernel_source_hash()},
+    }
+    if args.emulate_rank:
+        # one rank of the N-rank problem alone on one GPU: every rank does the same amount of work, the exchange is one
+        # all-gather of batch x (2L + 1) words per rank (latency-bound: ~20-40 us over xGMI), so the N-GPU step time is this
+        # rank's time plus that, and the predicted whole-job rate is the global unit count over it
+        result["emulated_rank"] = {"rank": shard_rank, "of": shard_world, "n_local": n_local, "whole_vectors": plan.whole, "sharded_vectors": plan.sharded,
+                                   "pairs_local": plan.pairs_local(),
+                                   "predicted_global_units_per_s_M": batch * n * args.steps / elapsed / 1e6,
+                                   "note": "value / ms_per_step are THIS rank's share (its whole vectors + its base range of the sharded ones) incl. the local copy standing in for the all-gather and the point sum"}
+    if not args.full:
+        # a plain run: the headline figure and nothing else (the rest below is --full)
+        if do_msm:
+            result["components"] = {"msm_window_bits": pre.window}
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps once more with HIP events on the launch stream around each kernel: the durations the rooflines use.
     # The events cost launches of their own (8 per MSM, 2 per NTT pass): this region is reported as ms_per_step_profiled, never as
@@ -299,12 +349,9 @@ def run(args):
     if world > 1 and args.workload == "both" and not args.timed_only:
         comp["multi_gpu"] = multi.multi_gpu_section(args, world, rank, gloo, sync, checks)
 
-    units_per_step = (n if do_ntt else 0) + (((plan.pairs_local() if args.emulate_rank else batch * n)) if do_msm else 0)
-    value = (1 if strong else world) * units_per_step * args.steps / elapsed / 1e6
-
     # ---- rooflines: every kernel entry carries the integer-ALU figure (what binds these kernels) and the HBM figure ----
     rooflines = {}
-    src_hash = kernel_source_hash()
+    src_hash = result["config"]["kernel_source_sha"]
     pmc = {}
     try:
         with open(latest_profile("pmc_traffic.json")) as fh:
@@ -360,37 +407,9 @@ def run(args):
     if rooflines:
         roofline = max(rooflines.values(), key=lambda r: r["launch_ms"] * (r.get("launches_per_transform", 1)))
 
-    wl = {"both": "2^%d %s forward NTT + 2^%d-pair %s MSM per GPU per step" % (args.log_n, "TweedledeeBase" if args.curve == "tweedledee" else "Bls12377Scalar", args.log_n, args.curve),
-          "ntt": "2^%d forward NTT per GPU per step" % args.log_n,
-          "msm": ("ONE 2^%d-pair %s MSM per step, generators sharded by base range over the GPUs" if strong else "2^%d-pair %s MSM per GPU per step") % (args.log_n, args.curve),
-          "commit9": "9-wire commitment batch: nine 2^%d-pair %s MSMs against the same generators per step (generators sharded by base range over the GPUs)" % (args.log_n, args.curve)}[args.workload]
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "M units/s (1 unit = 1 NTT element or 1 MSM scalar-point pair; components below)",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_profiled": elapsed_profiled / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": wl, "log_n": args.log_n, "curve": args.curve,
-                   "sharding": ("whole vectors per rank, the remainder sharded by base range; one packed all-gather + device point sum" if strong else
-                                "independent NTTs; MSM sharded by base range + one packed all-gather of partial points + device point sum") if world > 1 else "single GPU",
-                   "backend": ("gloo (ranks share GPU 0)" if gloo else "nccl (RCCL)") if world > 1 else None,
-                   "seeds": {"ntt": SEED_NTT, "msm": SEED_MSM}, "kernel_source_sha": src_hash, "gpu": gpu},
-        "components": comp,
-        "checks": checks,
-        "roofline": roofline,
-        "rooflines": rooflines,
-    }
-    if args.emulate_rank:
-        # one rank of the N-rank problem alone on one GPU: every rank does the same amount of work, the exchange is one
-        # all-gather of batch x (2L + 1) words per rank (latency-bound: ~20-40 us over xGMI), so the N-GPU step time is this
-        # rank's time plus that, and the predicted whole-job rate is the global unit count over it
-        result["emulated_rank"] = {"rank": shard_rank, "of": shard_world, "n_local": n_local, "whole_vectors": plan.whole, "sharded_vectors": plan.sharded,
-                                   "pairs_local": plan.pairs_local(),
-                                   "predicted_global_units_per_s_M": batch * n * args.steps / elapsed / 1e6,
-                                   "note": "value / ms_per_step are THIS rank's share (its whole vectors + its base range of the sharded ones) incl. the local copy standing in for the all-gather and the point sum"}
+    result["config"]["gpu"] = gpu
+    result.update({"ms_per_step_profiled": elapsed_profiled / args.steps * 1e3, "components": comp, "checks": checks, "roofline": roofline,
+                   "rooflines": rooflines})
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.emulate_rank:
         result["cpu_baseline"] = cpu_baseline(args.workload, cv)
     if rank == 0:

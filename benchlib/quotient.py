@@ -2,12 +2,12 @@
 import json
 import time
 
-from .common import HBM_PEAK_GBS, METRIC, Ceilings, gpu_identity, kernel_source_hash, latest_profile
+from .common import HBM_PEAK_GBS, METRIC, Ceilings, dump_outputs, gpu_identity, kernel_source_hash, latest_profile
 
 
 def run_quotient(args):
     """--workload quotient: k_vanishing_points (four launches per call), k_fold_pairs_glv and the 4-to-1 fold k_fold_multi_glv, timed with HIP events on the launch
-    stream, priced against the same ceilings as the headline kernels.  One GPU; correctness of both is the GPU suite's business
+    stream, priced against the same ceilings as the headline kernels (--full; a plain run times the numerator alone).  One GPU; correctness of both is the GPU suite's business
     (tests/test_gpu_plonk.py, tests/test_gpu_halo.py) - here the fold is checked by its closed form, the numerator by determinism."""
     import numpy as np
     import torch
@@ -62,9 +62,23 @@ def run_quotient(args):
 
     t0 = time.perf_counter()
     v_ms = timed(vanish, args.steps, args.warmup)
+    elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("vanishing_points", dev.to_host(out))])
+    result = {
+        "metric": METRIC, "value": n8 / (v_ms * 1e-3) / 1e6,
+        "unit": "M points/s of the quotient numerator (the fold is reported in components)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": v_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": "quotient numerator of a 2^%d-gate circuit (8n = 2^%d points) + generator fold of 2^%d pairs" % (log_degree, log_degree + 3, m.bit_length() - 1),
+                   "log_n": args.log_n, "curve": "tweedledee", "kernel_source_sha": kernel_source_hash()},
+    }
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        return
+    t0 = time.perf_counter()
     f_ms = timed(fold, max(1, args.steps // 2), 1)
     f4_ms = timed(fold4, max(1, args.steps // 2), 1) if fold4 else None
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     first = out.clone()
     vanish()
     g2, gz2 = fold()
@@ -93,7 +107,7 @@ def run_quotient(args):
             pmc = json.load(fh)
     except (OSError, ValueError):
         pass
-    src_hash = kernel_source_hash()
+    src_hash = result["config"]["kernel_source_sha"]
 
     def traffic(k):
         e = pmc.get(k)
@@ -123,16 +137,12 @@ def run_quotient(args):
                                         "~128 doublings (6M + 3S) per OUTPUT + ~64 mixed additions (8M + 2S, half of them with a multiplication by beta) per "
                                         "input + the inversions of the operand preparation and the affine result: ~3300 multiplications per output; "
                                         "units = outputs; launch_ms = digits + preparation + main kernel")
-    result = {
-        "metric": METRIC, "value": n8 / (v_ms * 1e-3) / 1e6,
-        "unit": "M points/s of the quotient numerator (the fold is reported in components)", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": v_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": "quotient numerator of a 2^%d-gate circuit (8n = 2^%d points) + generator fold of 2^%d pairs" % (log_degree, log_degree + 3, m.bit_length() - 1),
-                   "log_n": args.log_n, "curve": "tweedledee", "kernel_source_sha": src_hash, "gpu": gpu_identity(torch, 0)},
+    result["config"]["gpu"] = gpu_identity(torch, 0)
+    result.update({
         "components": {"vanishing_points_ms": v_ms, "vanishing_mpoints_per_s": n8 / (v_ms * 1e-3) / 1e6, "fold_pairs_ms": f_ms,
                        "fold_mpairs_per_s": m / (f_ms * 1e-3) / 1e6, "fold_4_to_1_ms": f4_ms,
                        "fold_4_to_1_minputs_per_s": (2 * m / (f4_ms * 1e-3) / 1e6) if f4_ms else None, "wall_s": elapsed},
         "checks": checks, "roofline": rooflines["vanishing_points"], "rooflines": rooflines,
-    }
+    })
     print(json.dumps(result), flush=True)
     assert all(checks.values()), "self-check failed: %r" % checks

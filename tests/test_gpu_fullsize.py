@@ -232,7 +232,7 @@ def test_bench_spawns_its_ranks(flags):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"] + flags, env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"] + flags, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -322,7 +322,8 @@ def test_bench_nccl_every_visible_gpu():
         pytest.skip("one GPU visible: RCCL with more than one rank needs a multi-GPU node")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(count), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--log-n", "18"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(count), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--log-n", "18",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -338,10 +339,43 @@ def test_bench_emulated_rank():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "commit9", "--log-n", "16", "--emulate-rank", "3/8", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=900)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     e = r["emulated_rank"]
     # nine vectors on eight ranks: one whole vector and an eighth of the ninth per rank (parallel.BatchPlan)
     assert e["rank"] == 3 and e["whole_vectors"] == 1 and e["sharded_vectors"] == 1 and e["pairs_local"] == (1 << 16) + (1 << 16) // 8
     assert all(r["checks"].values())
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` run: exactly --steps timed steps and the headline keys, none of --full's; --dump-outputs holds the
+    last step's results, which are the oracle's transform of the seeded input and the closed form of the seeded MSM."""
+    import json
+    import subprocess
+    import sys
+    from benchlib.common import SEED_MSM, SEED_NTT
+    from oracle import oracle_lib as ol
+    from plonky_amd.selfcheck import GENERATORS, _mul
+    from plonky_amd.synth import MODULI
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log_n = 14
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["higher_is_better"] is True and r["dtype"] == "u32" and r["unit"].startswith("M units/s")
+    assert not {"checks", "rooflines", "cpu_baseline", "ms_per_step_profiled"} & set(r)
+    n = 1 << log_n
+    ntt = np.load(tmp_path / "ntt_out.npy")
+    assert ntt.dtype == np.float64 and ntt.shape == (n, 8)
+    got = ntt.astype(np.uint32).view(np.uint64)
+    assert np.array_equal(got, ol.FftPrecomputation(0, n).fft_with_precomputation_power_of_2(synth.rand_field(0, SEED_NTT, n)))
+    xy = np.load(tmp_path / "msm_xy.npy").astype(np.uint32).view(np.uint64).reshape(2, 4)
+    assert not np.load(tmp_path / "msm_is_zero.npy").any()
+    G = GENERATORS[0]
+    D = _mul(MODULI[0], synth.to_int(synth.rand_field(1, SEED_MSM, 1)[0]) % MODULI[1], G)
+    assert (synth.from_mont(0, xy[0]), synth.from_mont(0, xy[1])) == closed_form_msm(0, synth.rand_field(1, SEED_MSM + 1, n), G, D, first=0)

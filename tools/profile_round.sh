@@ -8,16 +8,16 @@ RN=${1:-r04}
 export TMPDIR=/tmp; R="${GRAFT_REPO_ROOT:-$PWD}"; cd /tmp
 O=$R/gpurun_out
 rm -rf $O/prof_$RN $O/pmc_fetch $O/pmc_write $O/pmc_valu $O/prof_q $O/pmc_fetch_q $O/pmc_write_q
-rocprofv3 --kernel-trace --stats -d $O/prof_$RN -o bench -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --timed-only > $O/${RN}_bench_profiled_run.json 2> $O/prof_bench.err
+rocprofv3 --kernel-trace --stats -d $O/prof_$RN -o bench -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --timed-only --full > $O/${RN}_bench_profiled_run.json 2> $O/prof_bench.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --timed-only > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --timed-only > /dev/null 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace -d $O/pmc_valu -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --timed-only > /dev/null 2>&1
 # where the cycles of a wave go (one SQ pass, 8 slots): WAIT_ANY (parked on s_waitcnt / a barrier) + WAIT_INST_ANY (issue stall; WAIT_INST_LDS is
 # its LDS part) + ACTIVE_INST_ANY ~ WAVE_CYCLES, all in quad-cycles; ACTIVE_INST_VALU and the instruction counts beside them
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace -d $O/pmc_sq -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-check --timed-only > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $O/prof_q -o bench -- python $R/bench.py --workload quotient --steps 4 --warmup 1 > $O/${RN}_bench_quotient_profiled_run.json 2> $O/prof_q.err
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch_q -o bench -- python $R/bench.py --workload quotient --steps 2 --warmup 1 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write_q -o bench -- python $R/bench.py --workload quotient --steps 2 --warmup 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof_q -o bench -- python $R/bench.py --workload quotient --steps 4 --warmup 1 --full > $O/${RN}_bench_quotient_profiled_run.json 2> $O/prof_q.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch_q -o bench -- python $R/bench.py --workload quotient --steps 2 --warmup 1 --full > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write_q -o bench -- python $R/bench.py --workload quotient --steps 2 --warmup 1 --full > /dev/null 2>&1
 cd $R
 db() { find $1 -name "*.db" | head -1; }
 python tools/rocpd_summary.py $(db $O/prof_$RN) > $O/${RN}_rocprofv3_kernel_stats.txt 2>&1; head -30 $O/${RN}_rocprofv3_kernel_stats.txt
