@@ -187,6 +187,24 @@ int plk_plonk_vanishing_points_dev(int field, unsigned log_degree, const void* d
 int plk_plonk_vanishing_points(int field, unsigned log_degree, const uint64_t* constants_8n, const uint64_t* wires_8n, const uint64_t* s_sigma_8n,
                                const uint64_t* plonk_z_8n, const uint64_t* k_is, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                                const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out);
+/* permutation_polynomial (plonk_util.rs:234-262, called at plonk.rs:127-134): Z on the n-subgroup, n = 2^log_degree, g =
+ * primitive_root_of_unity(log_degree).  num_r = prod_j (w_j[r] + beta k_j g^r + gamma), den_r = prod_j (w_j[r] + beta sigma_j[r] + gamma)
+ * over the six routed wires; Z[0] = 1, Z[i] = Z[i - 1] num_(i-1) / den_(i-1) (rows 0..n-2 enter Z, row n - 1 only the wrap check).
+ * d_wires: wire_values_by_wire_index, [NUM_WIRES][n] (rows 0..5 are read).  d_s_sigma: 6 rows; sigma_j[r] is element
+ * (j n + r) sigma_stride - sigma_stride 8 takes s_sigma_values_8n as it is (the reference reads sigma_values[j][8 r]),
+ * sigma_stride 1 the n-point values of sigma_polynomials (plonk_util.rs:264-280); any other stride is PLK_ERR_INVALID_ARG.
+ * k_is[6], beta, gamma: host scalars as for plk_plonk_vanishing_points.  Fields: the 4-limb circuit scalar fields; log_degree <= 27.
+ * d_out: n elements, canonical Montgomery form.  d_status (nullable, device, 2 x uint32, written in stream order): [0] = zero
+ * denominators among rows 0..n-2 (Z unspecified when > 0), [1] = 1 iff the product of num_r / den_r over all n rows is 1 (every
+ * den_r nonzero): Z closes the cycle, i.e. the copy constraints hold.  Asynchronous on `stream`, the calling thread's device; the
+ * first call for a (field, log_degree) builds the circuit-size tables that plk_plonk_vanishing_points_dev shares. */
+int plk_plonk_permutation_z_dev(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                                const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, void* stream);
+/* Same with host pointers (wires: rows 0..5 are copied; sigma_stride 8: the n elements of a row the kernel reads are gathered on
+ * the host first, so 6 n elements cross PCIe in either form); PLK_ERR_INVALID_ARG with plk_last_error() starting "No inverse" where the
+ * reference panics (a zero den_r, r <= n - 2).  wraps_to_one (nullable): status word [1] above. */
+int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wires, const uint64_t* s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                            const uint64_t* beta, const uint64_t* gamma, uint64_t* out, int* wraps_to_one);
 /* evaluate_all_constraints (gates/mod.rs:46-125) at `count` independent points: constants [count][6], local / right / below
  * wire values [count][9] each, out [count][8] (the unified constraint set: the longest gate has 8 constraints). Host pointers. */
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,

@@ -464,6 +464,27 @@ def vanishing_points(field, degree, constants_8n, wire_values_8n, s_sigma_values
     return out
 
 
+def permutation_polynomial(field, degree, wire_values, s_sigma_values, k_is, beta, gamma, sigma_stride=8):
+    """permutation_polynomial (plonk_util.rs:234-262): Z on the n-subgroup, (n, 4).  wire_values: wire_values_by_wire_index,
+    (>= 6, n, 4) (rows 0..5 are read); s_sigma_values: (6, n * sigma_stride, 4) - s_sigma_values_8n with the default stride 8,
+    the n-point sigma values with stride 1.  A zero denominator in rows 0..n-2 panics in the reference ("No inverse") ->
+    AssertionError here."""
+    log_degree = log2_strict(degree)
+    assert sigma_stride in (1, 8), "sigma_stride must be 1 or 8"
+    w = np.asarray(wire_values, dtype=np.uint64).reshape(-1, degree, 4)
+    assert w.shape[0] >= NUM_ROUTED_WIRES
+    w = np.ascontiguousarray(w[:NUM_ROUTED_WIRES])
+    s = np.ascontiguousarray(s_sigma_values, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, degree * sigma_stride, 4)
+    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, 4)
+    b, g = (np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma))
+    out = np.empty((degree, 4), dtype=np.uint64)
+    rc = _lib.load().plk_plonk_permutation_z(field, log_degree, _ptr(w), _ptr(s), sigma_stride, _ptr(ks), _ptr(b), _ptr(g), _ptr(out), None)
+    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
+        raise AssertionError("No inverse")  # the reference panics (plonk_util.rs:259, field.rs Div)
+    _lib.check(rc)
+    return out
+
+
 # ---- batch inversion (field.rs:223-278, curve.rs:216-232) ----
 def batch_multiplicative_inverse(field, x):
     """Field::batch_multiplicative_inverse (field.rs:251-278): panics ("No inverse") on a zero element -> AssertionError here."""

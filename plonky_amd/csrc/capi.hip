@@ -6,6 +6,8 @@
 #include <cstdarg>
 #include <cstring>
 #include <map>
+#include <memory>
+#include <new>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -744,6 +746,50 @@ int plk_plonk_vanishing_points(int field, unsigned log_degree, const uint64_t* c
     PLK_TRY(c.tmp(dout, row));
     PLK_TRY(plonk_vanishing_points_dev_impl(field, log_degree, dc, dw, ds, dz, k_is, alpha, beta, gamma, inner_zeta, inner_a, dout, c.stream()));
     PLK_TRY(c.out(out, dout, row));
+    return c.finish();
+}
+int plk_plonk_permutation_z_dev(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                                const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, void* stream) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    return plonk_permutation_z_dev_impl(field, log_degree, d_wires, d_s_sigma, sigma_stride, k_is, beta, gamma, d_out, d_status, as_stream(stream));
+}
+int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wires, const uint64_t* s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                            const uint64_t* beta, const uint64_t* gamma, uint64_t* out, int* wraps_to_one) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    if (sigma_stride != 1 && sigma_stride != 8) return set_error(PLK_ERR_INVALID_ARG, "sigma_stride %u is neither 1 nor 8", sigma_stride);
+    if (log_degree + 3 > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_degree %u too large", log_degree);
+    if (!wires || !s_sigma || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t n = (size_t)1 << log_degree, row = n * 32;
+    // the kernel reads one sigma element in eight of an 8n table: gather those on the host, so that 6 n elements cross PCIe, not 6 * 8n
+    std::unique_ptr<uint64_t[]> gathered;
+    if (sigma_stride == 8) {
+        gathered.reset(new (std::nothrow) uint64_t[6 * n * 4]);
+        if (!gathered) return set_error(PLK_ERR_OOM, "host buffer of %zu bytes for the sigma rows", 6 * row);
+        for (size_t e = 0; e < 6 * n; ++e) memcpy(&gathered[e * 4], s_sigma + e * 8 * 4, 32);  // row j starts at j 8n = (j n) 8
+        s_sigma = gathered.get();
+    }
+    LaneCall c;  // after `gathered`: its destructor waits for the copies out of that buffer
+    PLK_TRY(c.begin());
+    c.pin(wires, 6 * row);  // rows 0..5 of wire_values_by_wire_index: the routed wires
+    c.pin(s_sigma, 6 * row);
+    c.pin(out, row);
+    void *dw = nullptr, *ds = nullptr, *dout = nullptr, *dst = nullptr;
+    PLK_TRY(c.in(dw, wires, 6 * row));
+    PLK_TRY(c.in(ds, s_sigma, 6 * row));
+    PLK_TRY(c.tmp(dout, row));
+    PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
+    PLK_TRY(plonk_permutation_z_dev_impl(field, log_degree, dw, ds, 1, k_is, beta, gamma, dout, dst, c.stream()));
+    uint32_t st[2] = {0, 0};
+    PLK_TRY(c.out(st, dst, sizeof(st)));
+    PLK_TRY(c.sync());
+    if (st[0]) {
+        c.done = true;
+        return set_error(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plonk_util.rs:259)", st[0]);
+    }
+    PLK_TRY(c.out(out, dout, row));
+    if (wraps_to_one) *wraps_to_one = (int)st[1];
     return c.finish();
 }
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,

@@ -144,6 +144,8 @@ int curve_batch_to_affine_dev_impl(int curve, size_t count, const void* d_xyz, c
 int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* d_constants, const void* d_wires, const void* d_s_sigma, const void* d_z,
                                     const uint64_t* k_is, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, const uint64_t* inner_zeta,
                                     const uint64_t* inner_a, void* d_out, hipStream_t stream);
+int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                                 const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, hipStream_t stream);
 int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_constants, const void* d_local, const void* d_right, const void* d_below,
                                    const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_out, hipStream_t stream);
 

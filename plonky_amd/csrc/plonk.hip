@@ -871,4 +871,213 @@ int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_consta
     return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
 }
 
+// ---------------------------------------------------------------------------------------------
+// permutation_polynomial (plonk_util.rs:234-262): the grand product Z of the copy-constraint argument
+// ---------------------------------------------------------------------------------------------
+// Z[0] = 1, Z[i] = Z[i - 1] num_(i-1) / den_(i-1) with num_r = prod_j (w_j[r] + beta k_j g^r + gamma) and
+// den_r = prod_j (w_j[r] + beta sigma_j[r] + gamma): Z is the EXCLUSIVE product scan of f_r = num_r / den_r over the n rows, and the
+// inclusive total (row n - 1 included) is 1 exactly when Z closes the cycle.  The reference walks the rows serially, one full
+// inversion per row; here it is a reduce-then-scan in three launches (no hand-off between workgroups inside a launch):
+//   k_perm_rows   a lane owns PERM_ROWS consecutive rows: their num / den, ONE inversion for the lane (Montgomery's trick on the
+//                 prefix products: f's exclusive prefixes are N_m / D_m), then a workgroup scan of the lane totals; writes the
+//                 tile-local exclusive prefixes (R'-form words) into the output and one total per tile;
+//   k_perm_tiles  one workgroup scans the tile totals (a run of consecutive tiles per lane, then the lanes) and writes the status;
+//   k_perm_fix    Z[i] = tile prefix x local prefix, in the reference's form.
+// A zero den_r is replaced by 1 and counted (as k_batch_inverse does); rows 0..n-2 are the reference's panic, row n - 1 never
+// enters Z and only spoils the wrap check.
+constexpr int PERM_ROWS = 8, PERM_LANES = 256, PERM_TILE = PERM_ROWS * PERM_LANES, PERM_SCAN_LANES = 1024;
+template <class P> using LzP = Lz<P, 9>;  // every product: below (9 / 8) p with exact limbs
+template <class P> PLK_DI LzP<P> lz_shfl_up(const LzP<P>& a, int d) {
+    LzP<P> r;
+#pragma unroll
+    for (int i = 0; i < FzCfg<P>::NZ; ++i) r.v.l[i] = __shfl_up(a.v.l[i], d);
+    return r;
+}
+// exclusive product scan of v over the workgroup (NW waves): wave shuffles, then the wave totals through LDS
+template <class P, int NW> PLK_DI LzP<P> wg_exclusive_product(LzP<P> v, uint32_t (*s_wave)[FzCfg<P>::NZ]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const LzP<P> one = lz_one<P>().template widen<9>();
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const LzP<P> o = lz_shfl_up<P>(v, d);
+        if (lane >= d) v = v * o;
+    }
+    LzP<P> ex = lz_shfl_up<P>(v, 1);
+    if (lane == 0) ex = one;
+    if (lane == 63) {
+#pragma unroll
+        for (int i = 0; i < FzCfg<P>::NZ; ++i) s_wave[w][i] = v.v.l[i];
+    }
+    __syncthreads();
+    for (int k = 0; k < w && k < NW; ++k) {
+        LzP<P> t;
+#pragma unroll
+        for (int i = 0; i < FzCfg<P>::NZ; ++i) t.v.l[i] = s_wave[k][i];
+        ex = ex * t;
+    }
+    return ex;
+}
+
+template <class P>
+__global__ void __launch_bounds__(PERM_LANES) k_perm_rows(const uint4* __restrict__ wires, const uint4* __restrict__ s_sigma, unsigned sigma_stride,
+                                                          const uint4* __restrict__ xs_lo_z, const uint4* __restrict__ xs_hi_z, PlonkScalars sc, int log_degree,
+                                                          uint4* __restrict__ out, uint32_t* __restrict__ tile_tot, unsigned* __restrict__ zeros,
+                                                          const uint32_t* __restrict__ top_table) {
+    static_assert(P::NL == 8, "256-bit scalar fields");
+    constexpr int NZ = FzCfg<P>::NZ;
+    using D = Lz<P, 16>;
+    __shared__ uint32_t s_sc[NUM_SCALARS][NZ];
+    __shared__ uint32_t s_bk[NUM_ROUTED_WIRES][NZ];
+    __shared__ uint32_t s_wave[PERM_LANES / 64][NZ];
+    __shared__ __attribute__((aligned(16))) LzTop<P> s_top;
+    stage_top_table<P>(top_table, s_top);
+    stage_scalars<P>(sc, s_sc);  // ends with the barrier that publishes both
+    if (threadIdx.x < NUM_ROUTED_WIRES) {  // beta k_j: one product per wire and row instead of two (plonk_util.rs:245)
+        const LzP<P> bk = scalar_at<P>(s_sc, 7) * scalar_at<P>(s_sc, threadIdx.x);
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) s_bk[threadIdx.x][i] = bk.v.l[i];
+    }
+    __syncthreads();
+    const size_t n = (size_t)1 << log_degree, n8 = n << 3;
+    const size_t r0 = ((size_t)blockIdx.x * PERM_LANES + threadIdx.x) * PERM_ROWS;
+    const D beta = scalar_at<P>(s_sc, 7), gamma = scalar_at<P>(s_sc, 8);
+    const LzP<P> one = lz_one<P>().template widen<9>();
+    // x = g_n^r = g_8n^(8 r) from the cached powers of the 8n-th root (hi[0] = 1), then one product by g_n = g_8n^8 per row
+    const size_t i8 = (r0 << 3) & (n8 - 1);
+    LzP<P> x = lz_table<P>(xs_lo_z, i8 & (((size_t)1 << XS_LO_LOG) - 1)) * lz_table<P>(xs_hi_z, i8 >> XS_LO_LOG);
+    const Lz<P, 8> g = lz_table<P>(xs_lo_z, 8);  // lo[j] = g_8n^(j mod 8n): 1 when n = 1
+    LzP<P> num_pre[PERM_ROWS], den[PERM_ROWS];  // num_pre[m] = N_(m+1) = prod_(k <= m) num_k
+    LzP<P> n_run = one, d_run = one;
+    unsigned z_head = 0, z_last = 0;
+#pragma unroll
+    for (int m = 0; m < PERM_ROWS; ++m) {
+        const size_t r = r0 + m;
+        LzP<P> num = one, de = one;
+        if (r < n) {
+#pragma unroll
+            for (int j = 0; j < NUM_ROUTED_WIRES; ++j) {
+                LzP<P> bk;
+#pragma unroll
+                for (int i = 0; i < NZ; ++i) bk.v.l[i] = s_bk[j][i];
+                const D w = lz_load<P>(wires, (size_t)j * n + r, s_top);
+                const D s = lz_load<P>(s_sigma, ((size_t)j * n + r) * sigma_stride, s_top);
+                num = num * (w + bk * x + gamma);
+                de = de * (w + beta * s + gamma);
+            }
+            if (fz_is_zero_mod_p<P>(de.v)) {  // field.rs "No inverse" for rows 0..n-2
+                de = one;
+                if (r + 1 < n) ++z_head;
+                else ++z_last;
+            }
+        }
+        x = x * g;
+        n_run = n_run * num;
+        num_pre[m] = n_run;
+        den[m] = de;
+        d_run = d_run * de;
+    }
+    // 1 / D_8 through the reference's form (the inversion works on the integer), back to R'-form limbs
+    LzP<P> inv = Lz<P, 8>{fz_from_fe<P>(fe_inv_safegcd<P>(lz_to_rform<P>(d_run)))} * Lz<P, 8>{fz_const_r_to_rprime<P>()};
+    const LzP<P> lane_total = num_pre[PERM_ROWS - 1] * inv;
+    LzP<P> e[PERM_ROWS];  // e[m] = N_m / D_m: the product of f over the lane's rows before m
+    e[0] = one;
+#pragma unroll
+    for (int m = PERM_ROWS - 1; m >= 1; --m) {
+        inv = inv * den[m];  // 1 / D_m
+        e[m] = num_pre[m - 1] * inv;
+    }
+    if (z_head) atomicAdd(&zeros[0], z_head);
+    if (z_last) atomicAdd(&zeros[1], z_last);
+    const LzP<P> ex = wg_exclusive_product<P, PERM_LANES / 64>(lane_total, s_wave);
+    if (threadIdx.x == PERM_LANES - 1) limbs_store<P>(tile_tot, blockIdx.x, (ex * lane_total).v);
+#pragma unroll
+    for (int m = 0; m < PERM_ROWS; ++m) {
+        if (r0 + m >= n) break;
+        const LzP<P> v = m == 0 ? ex : ex * e[m];
+        fe_store<P>(out + (r0 + m) * 2, fz_to_fe_canonical<P>(v.v));  // R'-form words, canonical (k_perm_fix reads them back)
+    }
+}
+
+// the tile totals -> exclusive tile prefixes (times R, so that k_perm_fix's one product lands in the reference's form); one workgroup
+template <class P>
+__global__ void __launch_bounds__(PERM_SCAN_LANES) k_perm_tiles(uint32_t* __restrict__ tile_tot, size_t tiles, const unsigned* __restrict__ zeros,
+                                                                uint32_t* __restrict__ status) {
+    __shared__ uint32_t s_wave[PERM_SCAN_LANES / 64][FzCfg<P>::NZ];
+    const LzP<P> one = lz_one<P>().template widen<9>();
+    const size_t per = (tiles + PERM_SCAN_LANES - 1) / PERM_SCAN_LANES;
+    const size_t b = (size_t)threadIdx.x * per, e = b + per < tiles ? b + per : tiles;
+    LzP<P> run = one;
+    for (size_t k = b; k < e; ++k) {
+        const LzP<P> v{limbs_load<P>(tile_tot, k)};
+        limbs_store<P>(tile_tot, k, run.v);
+        run = run * v;
+    }
+    const LzP<P> ex = wg_exclusive_product<P, PERM_SCAN_LANES / 64>(run, s_wave);
+    const LzP<P> c = ex * Lz<P, 8>{fz_const_rprime_to_r<P>()};
+    for (size_t k = b; k < e; ++k) limbs_store<P>(tile_tot, k, (LzP<P>{limbs_load<P>(tile_tot, k)} * c).v);
+    if (threadIdx.x == PERM_SCAN_LANES - 1 && status) {
+        const Fe<P> total = lz_to_rform<P>(ex * run), one_r = fe_one<P>();
+        bool is_one = true;
+#pragma unroll
+        for (int i = 0; i < P::NL; ++i) is_one = is_one && total.v[i] == one_r.v[i];
+        status[0] = zeros[0];
+        status[1] = zeros[0] == 0 && zeros[1] == 0 && is_one ? 1u : 0u;
+    }
+}
+
+template <class P> __global__ void __launch_bounds__(256) k_perm_fix(uint4* __restrict__ out, const uint32_t* __restrict__ tile_pre, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const LzP<P> z = lz_table<P>(out, i) * LzP<P>{limbs_load<P>(tile_pre, i / PERM_TILE)};
+    fe_store<P>(out + i * 2, fz_to_fe_canonical<P>(z.v));
+}
+
+template <class P>
+static int permutation_z_t(unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const PlonkScalars& sc, void* d_out,
+                           void* d_status, hipStream_t stream) {
+    std::shared_ptr<PlonkTables> t;
+    PLK_TRY(get_plonk_tables<P>((int)log_degree, stream, t));
+    const size_t n = (size_t)1 << log_degree, tiles = (n + PERM_TILE - 1) / PERM_TILE;
+    unsigned* zeros = (unsigned*)scratch_acquire(2 * sizeof(unsigned), stream);
+    if (!zeros) return PLK_ERR_OOM;
+    uint32_t* tile_tot = (uint32_t*)scratch_acquire(limb_bytes(tiles, FzCfg<P>::NZ), stream);
+    if (!tile_tot) {
+        scratch_release(zeros, stream);
+        return PLK_ERR_OOM;
+    }
+    hipError_t e = hipMemsetAsync(zeros, 0, 2 * sizeof(unsigned), stream);
+    if (e == hipSuccess) {
+        k_perm_rows<P><<<(unsigned)tiles, PERM_LANES, 0, stream>>>((const uint4*)d_wires, (const uint4*)d_s_sigma, sigma_stride, (const uint4*)t->xs_lo_z,
+                                                                   (const uint4*)t->xs_hi_z, sc, (int)log_degree, (uint4*)d_out, tile_tot, zeros,
+                                                                   (const uint32_t*)t->top);
+        k_perm_tiles<P><<<1, PERM_SCAN_LANES, 0, stream>>>(tile_tot, tiles, zeros, (uint32_t*)d_status);
+        k_perm_fix<P><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>((uint4*)d_out, tile_tot, n);
+        e = hipGetLastError();
+    }
+    scratch_release(tile_tot, stream);
+    scratch_release(zeros, stream);
+    if (e != hipSuccess) return set_error(PLK_ERR_HIP, "permutation Z launch failed: %s", hipGetErrorString(e));
+    return PLK_OK;
+}
+
+int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
+                                 const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, hipStream_t stream) {
+    if (!d_wires || !d_s_sigma || !d_out) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
+    if (!k_is || !beta || !gamma) return set_error(PLK_ERR_INVALID_ARG, "null challenge / shift pointer");
+    if (sigma_stride != 1 && sigma_stride != 8) return set_error(PLK_ERR_INVALID_ARG, "sigma_stride %u is neither 1 nor 8", sigma_stride);
+    if (log_degree + 3 > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_degree %u too large", log_degree);
+    PLK_TRY(ensure_device());
+    static const uint64_t zero4[4] = {0, 0, 0, 0};
+    PlonkScalars sc;
+    PLK_TRY(fill_scalars(sc, k_is, nullptr, beta, gamma, zero4, zero4));
+    switch (field) {
+        case PLK_FIELD_TWEEDLEDEE_BASE: return permutation_z_t<TweedledeeBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
+        case PLK_FIELD_TWEEDLEDUM_BASE: return permutation_z_t<TweedledumBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
+        case PLK_FIELD_BLS12_377_SCALAR: return permutation_z_t<Bls12377ScalarParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
+        case PLK_FIELD_PALLAS_BASE: return permutation_z_t<PallasBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
+        case PLK_FIELD_VESTA_BASE: return permutation_z_t<VestaBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
+    }
+    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+}
+
 }  // namespace plk

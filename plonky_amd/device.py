@@ -185,6 +185,33 @@ def vanishing_points_dev(field, log_degree, constants_8n, wire_values_8n, s_sigm
     return out
 
 
+def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k_is, beta, gamma, sigma_stride=8, out=None, status=None):
+    """permutation_polynomial (plonk_util.rs:234-262) on device-resident tables: int64 CUDA tensors wire_values (>= 6, n, 4)
+    (wire_values_by_wire_index; rows 0..5 are read) and s_sigma_values (6, n * sigma_stride, 4); the scalars are host arrays
+    (k_is (6, 4)).  Returns Z (n, 4); with status=True (or a (2,) int32 CUDA tensor) also the status words, written in stream
+    order: [0] zero denominators among rows 0..n-2 (Z unspecified when > 0), [1] 1 iff Z closes the cycle."""
+    n = 1 << log_degree
+    assert wire_values.is_cuda and wire_values.dtype == torch.int64 and wire_values.is_contiguous()
+    assert wire_values.numel() >= 6 * n * 4 and wire_values.numel() % (n * 4) == 0
+    assert s_sigma_values.is_cuda and s_sigma_values.dtype == torch.int64 and s_sigma_values.is_contiguous()
+    assert s_sigma_values.numel() == 6 * n * sigma_stride * 4
+    if out is None:
+        out = torch.empty((n, 4), dtype=torch.int64, device=wire_values.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == n * 4
+    want_status = status is not None and status is not False
+    if status is True:
+        status = torch.empty(2, dtype=torch.int32, device=wire_values.device)
+    if want_status:
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
+    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(6, 4)
+    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma)]
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().plk_plonk_permutation_z_dev(field, log_degree, ctypes.c_void_p(wire_values.data_ptr()), ctypes.c_void_p(s_sigma_values.data_ptr()),
+                                                       sigma_stride, p(ks), *[p(x) for x in sc], ctypes.c_void_p(out.data_ptr()),
+                                                       ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
+    return (out, status) if want_status else out
+
+
 # ---- one round of the inner-product argument (halo.rs:63-124) on device-resident vectors ----
 def _limbs(x, n=4):
     return np.ascontiguousarray(x, dtype=np.uint64).reshape(n)

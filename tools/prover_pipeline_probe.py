@@ -1,9 +1,10 @@
 """The hot-path calls of one Plonk proof (src/plonk.rs:85-200) strung together on the device, data resident in HBM
 between them: 9 wire iNTTs (values_to_polynomials), 9 LDEs to 8n (polynomials_to_values_padded), 9 blinded commitments
-(commit_polynomials), Z: one iNTT + LDE + commitment, the vanishing polynomial (vanishing_poly: the 8n-point constraint
+(commit_polynomials), Z: the grand product (permutation_polynomial) + one iNTT + LDE + commitment, the vanishing polynomial (vanishing_poly: the 8n-point constraint
 evaluation + one 8n iNTT), the quotient t = vanishing / Z_H (divide_by_z_h) and its 7 chunk commitments.
-The witness is an honest one (ArithmeticGate / ConstantGate rows with random selector constants, identity wiring, hence Z = 1), so
-the numerator is a REAL vanishing polynomial and the division by Z_H is checked to be exact (q * Z_H == vanishing).
+The witness is an honest one (ArithmeticGate / ConstantGate rows with random selector constants) with real copy constraints: the
+routed wires draw their values from a small pool, every set of cells holding one value is one cycle of the wiring, and sigma maps a
+cell to the next one of its cycle (hence Z is not constant, and its wrap check holds), so the numerator is a REAL vanishing polynomial and the division by Z_H is checked to be exact (q * Z_H == vanishing).
 Witness generation and the transcript are not part of this probe.  With `ipa` the rounds of the opening's inner-product argument
 (halo.rs:63-124) follow, over the SAME tables - built over the circuit's fixed generators [pedersen_g, pedersen_h, U] (plonk.rs:46-51)
 - with stand-in challenges.  Usage (GPU box): python tools/prover_pipeline_probe.py [log_n] [ipa]"""
@@ -30,6 +31,8 @@ print("setup: msm_precompute of %d generators %.1f ms (once per circuit)" % (n +
 # ---- an honest witness: ArithmeticGate rows (arithmetic.rs:32-46): w3 = c0 w0 w1 + c1 w2, selector constants 1001 c0 c1 ----
 ONE, ZERO = synth.mont(F, 1), synth.mont(F, 0)
 w = synth.rand_field(F, 1, 9 * n).reshape(9, n, 4)
+pool_rng = np.random.default_rng(3)
+w[:6] = synth.rand_field(F, 4, 1024)[pool_rng.integers(0, 1024, size=6 * n)].reshape(6, n, 4)   # repeated values: copy constraints
 c0, c1 = synth.rand_field(F, 7, n), synth.rand_field(F, 8, n)
 w[3] = api.field_op(F, "add", api.field_op(F, "mul", api.field_op(F, "mul", c0, w[0]), w[1]), api.field_op(F, "mul", c1, w[2]))
 consts = np.stack([np.tile(ONE, (n, 1)), np.tile(ZERO, (n, 1)), np.tile(ZERO, (n, 1)), np.tile(ONE, (n, 1)), c0, c1])
@@ -39,17 +42,30 @@ w[0, 1::2] = c1[1::2]
 k_is = synth.rand_field(F, 9, 6)                                                   # get_subgroup_shift(0..5): inputs
 alpha, beta, gamma = synth.rand_field(F, 10, 3)
 ZETA = np.array([7605997034305223424, 3132214451552427455, 3308921103222877309, 2709928666517121162], dtype=np.uint64)  # tweedledum_curve.rs:37-44
-# circuit-constant 8n tables (circuit_builder.rs:1135-1160): constants, S_sigma_j = k_j X (identity wiring)
+# circuit-constant 8n tables (circuit_builder.rs:1135-1160): constants, and the wiring: the cells (j, r) of the routed wires that
+# hold one value form one cycle, sigma_j[r] = k_j' g^r' of the next cell (j', r') (sigma_polynomials, plonk_util.rs:264-280)
 t0 = time.perf_counter()
 const_coeffs = dev.ntt_dev(F, dev.to_device(consts), inverse=True)
 consts_8n = dev.ntt_padded_dev(F, const_coeffs, log_n + 3)
-sig = np.zeros((6, 2, 4), dtype=np.uint64); sig[:, 1] = k_is
-sigma_8n = dev.ntt_padded_dev(F, dev.to_device(sig), log_n + 3)
+sig = np.zeros((6, n, 4), dtype=np.uint64); sig[:, 1] = k_is
+ident = dev.to_host(dev.ntt_dev(F, dev.to_device(sig))).reshape(6 * n, 4)          # k_j g^r, row r
+key = np.unique(np.ascontiguousarray(w[:6]).reshape(6 * n, 4).view("V32").ravel(), return_inverse=True)[1].ravel()
+order = np.argsort(key, kind="stable")
+ks = key[order]
+new_group = np.insert(ks[1:] != ks[:-1], 0, True)
+first = np.maximum.accumulate(np.where(new_group, np.arange(6 * n), 0))
+succ = np.arange(1, 6 * n + 1)
+last = np.append(new_group[1:], True)
+succ[last] = first[last]
+nxt = np.empty(6 * n, dtype=np.int64); nxt[order] = order[succ]
+sigma_n = dev.to_device(ident[nxt].reshape(6, n, 4))
+sigma_8n = dev.ntt_padded_dev(F, dev.ntt_dev(F, sigma_n, inverse=True), log_n + 3)   # s_sigma_values_8n
 torch.cuda.synchronize()
 print("setup: constants_8n / s_sigma_values_8n %.1f ms (once per circuit)" % ((time.perf_counter() - t0) * 1e3))
 wires = dev.to_device(w)
 blind = torch.cat([dev.to_device(synth.rand_field(F, 2, 9 + 1 + 7)).reshape(-1, 1, 4), torch.zeros((17, 1, 4), dtype=torch.int64, device="cuda")], dim=1)  # [r] H + [0] U
-zvals = dev.to_device(np.tile(ONE, (n, 1)))                                         # identity wiring: Z = 1
+zvals = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+zstatus = torch.empty(2, dtype=torch.int32, device="cuda")
 t_out = torch.empty((8 * n, 4), dtype=torch.int64, device="cuda")
 ev8 = torch.empty((9, 8 * n, 4), dtype=torch.int64, device="cuda")
 pts = torch.empty((8 * n, 4), dtype=torch.int64, device="cuda")
@@ -65,6 +81,8 @@ def run():
     marks[2].record()
     c_wires = dev.msm_execute_dev(pre, torch.cat([polys, blind[:9]], dim=1).contiguous())   # commit_polynomials (+ [r] H)
     marks[3].record()
+    dev.permutation_polynomial_dev(F, log_n, wires, sigma_8n, k_is, beta, gamma, sigma_stride=8, out=zvals, status=zstatus)   # plonk.rs:127-134
+    marks[8].record()
     zpoly = dev.ntt_dev(F, zvals, inverse=True)
     z_8n = dev.ntt_padded_dev(F, zpoly, log_n + 3)                                  # plonk.rs:388-391
     c_z = dev.msm_execute_dev(pre, torch.cat([zpoly, blind[9]], dim=0).contiguous())
@@ -80,9 +98,10 @@ def run():
     c_t = dev.msm_execute_dev(pre, torch.cat([chunks, blind[10:17]], dim=1).contiguous())
     marks[7].record()
     torch.cuda.synchronize()
-    names = ["9 wire iNTT (n)", "9 LDE n -> 8n", "9 wire commitments", "Z: iNTT + LDE + commitment", "vanishing points (8n, 10 gates)",
-             "iNTT (8n) + divide_by_z_h", "7 quotient-chunk commitments"]
-    ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(7)]
+    names = ["9 wire iNTT (n)", "9 LDE n -> 8n", "9 wire commitments", "Z: grand product (n, stride 8)", "Z: iNTT + LDE + commitment",
+             "vanishing points (8n, 10 gates)", "iNTT (8n) + divide_by_z_h", "7 quotient-chunk commitments"]
+    seq = [0, 1, 2, 3, 8, 4, 5, 6, 7]
+    ms = [marks[seq[i]].elapsed_time(marks[seq[i + 1]]) for i in range(8)]
     return names, ms, t, vanishing
 
 
@@ -93,6 +112,9 @@ v = dev.to_host(vanishing)
 zpad = np.zeros((n, 4), dtype=np.uint64)
 back = api.field_op(F, "sub", np.concatenate([zpad, q]), np.concatenate([q, zpad]))   # q * (X^n - 1)
 ok = bool(v.any() and not dev.to_host(t)[7 * n:].any() and np.array_equal(back, v))
+zh = dev.to_host(zvals)
+print("Z: status %s (zero denominators, wraps to 1), distinct values among the first 1024 rows: %d" % (zstatus.cpu().tolist(), len({r.tobytes() for r in zh[:1024]})))
+print("q * Z_H == vanishing: %s" % ok)
 for nm, tv in zip(names, ms):
     print("  %-34s %8.3f ms" % (nm, tv))
 print("hot-path device time per proof at n = 2^%d: %.2f ms   (real numerator; q * Z_H == vanishing polynomial, deg q < 7n: %s)" % (log_n, sum(ms), ok))
