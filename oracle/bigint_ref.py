@@ -473,28 +473,49 @@ def plonk_eval_l_1(f: FieldSpec, n, x):
     return (pow(x, n, f.p) - 1) * pow(n * (x - 1), -1, f.p) % f.p
 
 
+def plonk_vanishing_point_reads(degree, i):
+    """The table entries point i of the 8 * degree-point loop reads, in the order plonk_vanishing_point reads them: (table, row, index)
+    with table one of "constants", "wires", "s_sigma", "z" (row 0 for z)."""
+    n8 = 8 * degree
+    ir, ib = (i + 8) % n8, (i + 8 * GRID_WIDTH) % n8
+    return ([("constants", j, i) for j in range(NUM_CONSTANTS)] + [("wires", j, idx) for idx in (i, ir, ib) for j in range(NUM_WIRES)]
+            + [("s_sigma", j, i) for j in range(NUM_ROUTED_WIRES)] + [("z", 0, i), ("z", 0, ir)])
+
+
+def plonk_vanishing_point(f: FieldSpec, degree, i, constants, wires, s_sigma, z, k_is, alpha, beta, gamma, zeta, a, g=None):
+    """Point i of plonk.rs:392-453 on canonical integers: x = g^i with g the primitive 8 * degree-th root, the right gate at
+    (i + 8) mod 8n, the gate below at (i + 8 GRID_WIDTH) mod 8n.  The tables are accessors: constants(j, idx), wires(j, idx),
+    s_sigma(j, idx) and z(idx) return the canonical value of row j at point idx."""
+    p, n8 = f.p, 8 * degree
+    if g is None:
+        g = f.primitive_root_of_unity(n8.bit_length() - 1)
+    x = pow(g, i, p)
+    ir, ib = (i + 8) % n8, (i + 8 * GRID_WIDTH) % n8
+    k = [constants(j, i) for j in range(NUM_CONSTANTS)]
+    l = [wires(j, i) for j in range(NUM_WIRES)]
+    r = [wires(j, ir) for j in range(NUM_WIRES)]
+    b = [wires(j, ib) for j in range(NUM_WIRES)]
+    z_x, z_gx = z(i), z(ir)
+    terms = [plonk_eval_l_1(f, degree, x) * (z_x - 1) % p]
+    fp = gp = 1
+    for j in range(NUM_ROUTED_WIRES):
+        fp = fp * (l[j] + beta * k_is[j] * x + gamma) % p
+        gp = gp * (l[j] + beta * s_sigma(j, i) + gamma) % p
+    terms.append((fp * z_x - gp * z_gx) % p)
+    terms += plonk_all_constraints(f, k, l, r, b, zeta, a)
+    acc = 0
+    for t in reversed(terms):
+        acc = (acc * alpha + t) % p
+    return acc
+
+
+def plonk_vanishing_points_at(f: FieldSpec, degree, rows, constants, wires, s_sigma, z, k_is, alpha, beta, gamma, zeta, a):
+    """plonk_vanishing_point at each point of `rows` (accessor tables as there)."""
+    g = f.primitive_root_of_unity((8 * degree).bit_length() - 1)
+    return [plonk_vanishing_point(f, degree, i, constants, wires, s_sigma, z, k_is, alpha, beta, gamma, zeta, a, g=g) for i in rows]
+
+
 def plonk_vanishing_points(f: FieldSpec, degree, constants, wires, s_sigma, z, k_is, alpha, beta, gamma, zeta, a):
     """plonk.rs:392-453 on canonical integers; tables are lists of rows of 8 * degree values."""
-    p, n8 = f.p, 8 * degree
-    g = f.primitive_root_of_unity(n8.bit_length() - 1)
-    out = []
-    x = 1
-    for i in range(n8):
-        ir, ib = (i + 8) % n8, (i + 8 * GRID_WIDTH) % n8
-        k = [constants[j][i] for j in range(NUM_CONSTANTS)]
-        l = [wires[j][i] for j in range(NUM_WIRES)]
-        r = [wires[j][ir] for j in range(NUM_WIRES)]
-        b = [wires[j][ib] for j in range(NUM_WIRES)]
-        terms = [plonk_eval_l_1(f, degree, x) * (z[i] - 1) % p]
-        fp = gp = 1
-        for j in range(NUM_ROUTED_WIRES):
-            fp = fp * (l[j] + beta * k_is[j] * x + gamma) % p
-            gp = gp * (l[j] + beta * s_sigma[j][i] + gamma) % p
-        terms.append((fp * z[i] - gp * z[ir]) % p)
-        terms += plonk_all_constraints(f, k, l, r, b, zeta, a)
-        acc = 0
-        for t in reversed(terms):
-            acc = (acc * alpha + t) % p
-        out.append(acc)
-        x = x * g % p
-    return out
+    return plonk_vanishing_points_at(f, degree, range(8 * degree), lambda j, i: constants[j][i], lambda j, i: wires[j][i],
+                                     lambda j, i: s_sigma[j][i], lambda i: z[i], k_is, alpha, beta, gamma, zeta, a)

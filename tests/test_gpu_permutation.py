@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from plonky_amd import api
 from oracle import bigint_ref as br
+from oracle import oracle_lib as ol
 from tests.test_oracle_plonk import ZETA_MONT, mont, unmont
 
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
@@ -204,8 +205,10 @@ def check_honest_z(f, log_n, w_host, sigma, z, k, beta, gamma, seed):
     assert z_i(n - 1) * num % p == den
 
 
-@pytest.mark.parametrize("log_n", [16, 20])
+@pytest.mark.parametrize("log_n", [16, 20, 22])
 def test_honest_permutation_closes(log_n):
+    """A satisfied copy-constraint table closes the cycle.  At 2^22 rows there are 2048 tiles of 2048 rows: every lane of the tile scan
+    (k_perm_tiles, 1024 lanes) carries two of them."""
     from plonky_amd import device as dev
     dev.init(0)
     f, n = br.TWEEDLEDUM_BASE, 1 << log_n
@@ -226,6 +229,72 @@ def test_honest_permutation_closes(log_n):
     bad[a], bad[b] = sigma[b].copy(), sigma[a].copy()
     _, st = dev.permutation_polynomial_dev(f.field_id, log_n, dw, dev.to_device(bad), km, bm, gm, sigma_stride=1, status=True)
     assert st.cpu().tolist()[1] == 0
+
+
+LARGE_FIELDS = [br.TWEEDLEDEE_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
+
+
+@pytest.mark.parametrize("log_n,stride", [(21, 8), (22, 1)], ids=["2p21-stride8", "2p22-stride1"])
+@pytest.mark.parametrize("f", LARGE_FIELDS, ids=lambda f: f.name)
+def test_z_random_large_n(f, log_n, stride):
+    """Random wires and sigma drawn on the device (every element independent).  2^21 rows: 1024 tiles, exactly one per lane of the
+    tile scan, sigma read with stride 8 from an 8n table; 2^22 rows: two tiles per scan lane.  The recurrence
+    z[i] den[i-1] == z[i-1] num[i-1] is checked with big integers at every tile boundary i = 2048 k (the steps within a scan lane and
+    between lanes) and at 1024 seeded random rows; z[0] = 1, no zero denominator, and status[1] is what the returned Z says."""
+    import torch
+    from plonky_amd import device as dev
+    from tests.test_gpu_plonk_fullsize import clear_device_caches, device_words
+    dev.init(0)
+    p, n = f.p, 1 << log_n
+    seed = 0x2B16 + 16 * log_n + f.field_id
+    rng = random.Random(seed)
+    km = ol.rand_field(f.field_id, seed, 8)
+    km, bm, gm = km[:6], km[6], km[7]
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(seed)
+    tile = 2048
+    boundaries = list(range(tile, n, tile))
+    assert len(boundaries) == n // tile - 1
+    checked = sorted(set(boundaries) | set(rng.sample(range(1, n), 1024)) | {n - 1})
+    rows = sorted(set(checked) | {i - 1 for i in checked} | {0})
+    try:
+        w = device_words(f, (6, n), gen)
+        s = device_words(f, (6, n * stride), gen)
+        z, st = dev.permutation_polynomial_dev(f.field_id, log_n, w, s, km, bm, gm, sigma_stride=stride, status=True)
+        r_t = torch.tensor(rows, dtype=torch.int64, device="cuda")
+        wh = dev.to_host(w[:, r_t])
+        sh = dev.to_host(s.view(6, n, stride, 4)[:, r_t, 0])
+        zh = dev.to_host(z[r_t])
+        status = [int(v) for v in st.cpu().tolist()]
+    finally:
+        w = s = z = None
+        clear_device_caches()
+    at = {r: c for c, r in enumerate(rows)}
+    canon = lambda v: f.from_mont(br.limbs_to_int(v))
+    k = [canon(km[j]) for j in range(6)]
+    beta, gamma = canon(bm), canon(gm)
+    g = f.primitive_root_of_unity(log_n)
+    assert all(br.limbs_to_int(v) < p for v in zh), "Z words are not canonical"
+    z_i = lambda r: canon(zh[at[r]])
+
+    def nd(r):
+        x, num, den = pow(g, r, p), 1, 1
+        for j in range(6):
+            wv, sv = canon(wh[j, at[r]]), canon(sh[j, at[r]])
+            num = num * (wv + beta * k[j] * x + gamma) % p
+            den = den * (wv + beta * sv + gamma) % p
+        return num, den
+
+    assert br.limbs_to_int(zh[at[0]]) == f.to_mont(1)
+    assert status[0] == 0
+    bad = []
+    for i in checked:
+        num, den = nd(i - 1)
+        if z_i(i) * den % p != z_i(i - 1) * num % p:
+            bad.append(i)
+    assert not bad, "%d of %d checked rows break the recurrence, first %s" % (len(bad), len(checked), bad[:8])
+    num, den = nd(n - 1)
+    assert status[1] == int(z_i(n - 1) * num % p == den)
 
 
 @pytest.mark.parametrize("where", ["middle", "last"])

@@ -13,7 +13,7 @@ from oracle import bigint_ref as br
 from oracle import oracle_lib as ol
 from tests.test_oracle_plonk import ZETA_MONT, _random_tables, mont
 
-FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR]
+FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 
 
 @pytest.mark.parametrize("f", FIELDS, ids=lambda f: f.name)

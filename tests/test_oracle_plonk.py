@@ -21,7 +21,7 @@ INNER = br.TWEEDLEDUM
 # InnerC::ZETA, tweedledum_curve.rs:37-44 (Montgomery limbs); InnerC::A = 0 (tweedledum_curve.rs:11)
 ZETA_MONT = [7605997034305223424, 3132214451552427455, 3308921103222877309, 2709928666517121162]
 ZETA = F.from_mont(br.limbs_to_int(ZETA_MONT))
-FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR]
+FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 N_GATES = len(br.PLONK_GATES)
 
 
@@ -178,6 +178,33 @@ def test_vanishing_points_match_bigint_restatement(f, degree):
     exp = br.plonk_vanishing_points(f, degree, rows(consts), rows(wires), rows(sigma), unmont(f, z), unmont(f, k_is), one(alpha), one(beta),
                                     one(gamma), one(zeta), one(a))
     assert got == exp
+
+
+@pytest.mark.parametrize("f", FIELDS, ids=lambda f: f.name)
+@pytest.mark.parametrize("degree", [1, 2, 8, 128])
+def test_vanishing_point_sampled_matches_full_loop(f, degree):
+    """br.plonk_vanishing_point, the one-row form the full-size GPU tests sample with, evaluated at every row through accessors that
+    read the stored words, against the whole-domain loop on canonical lists and against the oracle."""
+    consts, wires, sigma, z, k_is, alpha, beta, gamma, zeta, a = _random_tables(f, degree, 0x5A3 + degree)
+    word = lambda v: f.from_mont(br.limbs_to_int(v))
+    one = lambda v: unmont(f, v.reshape(1, 4))[0]
+    scal = (unmont(f, k_is), one(alpha), one(beta), one(gamma), one(zeta), one(a))
+    sampled = br.plonk_vanishing_points_at(f, degree, range(8 * degree), lambda j, i: word(consts[j, i]), lambda j, i: word(wires[j, i]),
+                                           lambda j, i: word(sigma[j, i]), lambda i: word(z[i]), *scal)
+    rows = lambda t: [unmont(f, t[j]) for j in range(t.shape[0])]
+    full = br.plonk_vanishing_points(f, degree, rows(consts), rows(wires), rows(sigma), unmont(f, z), *scal)
+    exp = unmont(f, ol.vanishing_points(f.field_id, degree, consts, wires, sigma, z, k_is, alpha, beta, gamma, zeta, a, threads=4))
+    assert len(sampled) == 8 * degree
+    assert sampled == full
+    assert sampled == exp
+
+
+def test_vanishing_point_reads():
+    """The read list of a point: 41 entries, the right / below neighbours wrap around the domain."""
+    reads = br.plonk_vanishing_point_reads(2, 15)
+    assert len(reads) == 6 + 3 * 9 + 6 + 2
+    assert {idx for t, _, idx in reads if t == "wires"} == {15, (15 + 8) % 16, (15 + 8 * br.GRID_WIDTH) % 16}
+    assert [r for r in reads if r[0] == "z"] == [("z", 0, 15), ("z", 0, 7)]
 
 
 def extreme_words(f):
