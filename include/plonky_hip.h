@@ -210,6 +210,36 @@ int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wire
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out);
 
+/* ---- the opening step  (src/plonk.rs:261-308, src/halo.rs:38-44 and 143-155, src/plonk_util.rs:123-133 and 311-326) ------------- */
+/* Everything between the commitments and the first round of the inner-product argument.  All of it is exact field arithmetic, so
+ * every output is the reference's word for word.  The _dev forms are asynchronous on `stream`, do not synchronise, leave their
+ * inputs unchanged and take their working memory from the library's scratch pool; scalars (points, v, s_i, u_j) are HOST arrays
+ * of 4 limbs each, Montgomery form.  The forms without _dev take host pointers for the data as well.  Fields: the five 4-limb fields.
+ *
+ * powers (plonk_util.rs:123-133): out[j] = x^j, j < count (x = 0 gives 1, 0, 0, ...). */
+int plk_field_powers_dev(int field, const uint64_t* x, size_t count, void* d_out, void* stream);
+int plk_field_powers(int field, const uint64_t* x, size_t count, uint64_t* out);
+/* open_all_polynomials (plonk.rs:261-284, 459-482) = eval_polys (plonk_util.rs:153-155) for every opening point at once:
+ * d_out[k * n_polys + i] = sum_j c_i[j] x_k^j = polys[i].eval_from_power(powers(x_k, lens[i])).  d_polys: HOST array of n_polys device
+ * pointers (the polynomials live in different buffers; the same pointer may appear twice), lens[i] >= 0 coefficients each (any
+ * length), 1 <= n_points <= 8 points.  Every polynomial is read from device memory once, for all points; no power vector exists. */
+int plk_plonk_eval_polys_dev(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, unsigned n_points, const uint64_t* points, void* d_out,
+                             void* stream);
+int plk_plonk_eval_polys(int field, unsigned n_polys, const uint64_t* const* polys, const size_t* lens, unsigned n_points, const uint64_t* points, uint64_t* out);
+/* reduced_coeffs of batch_opening_proof (halo.rs:38-44), the argument's halo_a: d_out[j] = sum_i scalars[i] c_i[j], j < degree; a
+ * polynomial shorter than `degree` counts as zero-padded, a longer one is PLK_ERR_INVALID_ARG (the reference asserts).  One pass. */
+int plk_poly_reduce_dev(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, const uint64_t* scalars, size_t degree, void* d_out,
+                        void* stream);
+int plk_poly_reduce(int field, unsigned n_polys, const uint64_t* const* polys, const size_t* lens, const uint64_t* scalars, size_t degree, uint64_t* out);
+/* build_halo_b (halo.rs:143-155), the argument's halo_b: d_out[j] = reduce_with_powers([x_0^j, x_1^j, ...], v) = sum_k v^k x_k^j,
+ * j < degree, 1 <= n_points <= 8. */
+int plk_halo_build_b_dev(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, void* d_out, void* stream);
+int plk_halo_build_b(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, uint64_t* out);
+/* halo_s (plonk_util.rs:311-326; OldProof::coeffs): 2^k elements, element i = prod_j (bit j of i ? us : 1 / us)[k - 1 - j], k <= 30.
+ * The k inversions happen inside; a zero among `us` is PLK_ERR_INVALID_ARG with plk_last_error() starting "No inverse". */
+int plk_halo_s_dev(int field, unsigned k, const uint64_t* us, void* d_out, void* stream);
+int plk_halo_s(int field, unsigned k, const uint64_t* us, uint64_t* out);
+
 /* ---- MSM  (src/curve/curve_msm.rs) -------------------------------------------------------- */
 typedef struct plk_msm_ctx plk_msm_ctx;
 

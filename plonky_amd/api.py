@@ -485,6 +485,66 @@ def permutation_polynomial(field, degree, wire_values, s_sigma_values, k_is, bet
     return out
 
 
+# ---- the opening step (plonk.rs:261-308, halo.rs:38-44 and 143-155, plonk_util.rs:123-133 and 311-326) ----
+def _poly_args(polys):
+    """list of (len, 4) limb arrays -> (kept arrays, ctypes array of host pointers, lengths)"""
+    arrs = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+    ptrs = (ctypes.c_void_p * max(1, len(arrs)))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
+    lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)  # size_t
+    return arrs, ptrs, lens
+
+
+def powers(field, x, n):
+    """powers (plonk_util.rs:123-133): [1, x, ..., x^(n-1)] as (n, 4)."""
+    xs = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+    out = np.empty((n, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_field_powers(field, _ptr(xs), n, _ptr(out)))
+    return out
+
+
+def eval_polys(field, polys, points):
+    """open_all_polynomials (plonk.rs:459-482): out[k][i] = polys[i].eval_from_power(powers(points[k], len(polys[i]))), (n_points, n_polys, 4).
+    polys: a list of (len, 4) coefficient arrays of any lengths; 1..8 points."""
+    arrs, ptrs, lens = _poly_args(polys)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    out = np.empty((pts.shape[0], len(arrs), 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_plonk_eval_polys(field, len(arrs), ptrs, _ptr(lens), pts.shape[0], _ptr(pts), _ptr(out)))
+    return out
+
+
+def reduce_polynomials(field, polys, scalars, degree):
+    """reduced_coeffs of batch_opening_proof (halo.rs:38-44): out[j] = sum_i scalars[i] * polys[i][j], (degree, 4); a polynomial longer
+    than `degree` trips the reference's assertion -> AssertionError here."""
+    arrs, ptrs, lens = _poly_args(polys)
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    assert sc.shape[0] == len(arrs), "one scalar per polynomial"
+    assert all(a.shape[0] <= degree for a in arrs), "polynomial longer than the degree"
+    out = np.empty((degree, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_poly_reduce(field, len(arrs), ptrs, _ptr(lens), _ptr(sc), degree, _ptr(out)))
+    return out
+
+
+def build_halo_b(field, points, v, degree):
+    """build_halo_b (halo.rs:143-155): out[j] = sum_k v^k points[k]^j, (degree, 4)."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    vs = np.ascontiguousarray(v, dtype=np.uint64).reshape(4)
+    out = np.empty((degree, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_halo_build_b(field, pts.shape[0], _ptr(pts), _ptr(vs), degree, _ptr(out)))
+    return out
+
+
+def halo_s(field, us):
+    """halo_s (plonk_util.rs:311-326): the 2^k coefficients of g(X, us).  A zero challenge has no inverse: the reference panics
+    ("No inverse", field.rs:266) -> AssertionError here."""
+    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    out = np.empty((1 << u.shape[0], 4), dtype=np.uint64)
+    rc = _lib.load().plk_halo_s(field, u.shape[0], _ptr(u), _ptr(out))
+    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
+        raise AssertionError("No inverse")
+    _lib.check(rc)
+    return out
+
+
 # ---- batch inversion (field.rs:223-278, curve.rs:216-232) ----
 def batch_multiplicative_inverse(field, x):
     """Field::batch_multiplicative_inverse (field.rs:251-278): panics ("No inverse") on a zero element -> AssertionError here."""

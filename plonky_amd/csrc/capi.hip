@@ -811,6 +811,123 @@ int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* 
     return c.finish();
 }
 
+// ---- the opening step: evaluations, the reduced polynomial, halo_b, halo_s, powers (opening.hip) ----
+int plk_field_powers_dev(int field, const uint64_t* x, size_t count, void* d_out, void* stream) {
+    PLK_API;
+    if (!x) return set_error(PLK_ERR_INVALID_ARG, "null pointer: x");
+    static const uint64_t unused_v[4] = {0, 0, 0, 0};  // v^0 = 1 is the only power of v one point takes
+    return halo_build_b_dev_impl(field, 1, x, unused_v, count, d_out, as_stream(stream));
+}
+int plk_field_powers(int field, const uint64_t* x, size_t count, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    if (!x || (count && !out)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(out, count * 32);
+    void* dout = nullptr;
+    PLK_TRY(c.tmp(dout, count * 32));
+    static const uint64_t unused_v[4] = {0, 0, 0, 0};
+    PLK_TRY(halo_build_b_dev_impl(field, 1, x, unused_v, count, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, count * 32));
+    return c.finish();
+}
+int plk_plonk_eval_polys_dev(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, unsigned n_points, const uint64_t* points, void* d_out,
+                             void* stream) {
+    PLK_API;
+    return plonk_eval_polys_dev_impl(field, n_polys, d_polys, lens, n_points, points, d_out, as_stream(stream));
+}
+// the polynomials of a host-pointer call, uploaded one by one on the lane
+static int lane_upload_polys(LaneCall& c, unsigned n_polys, const uint64_t* const* polys, const size_t* lens, std::vector<const void*>& dev) {
+    dev.assign(n_polys, nullptr);
+    for (unsigned i = 0; i < n_polys; ++i) {
+        if (lens[i] && !polys[i]) return set_error(PLK_ERR_INVALID_ARG, "null pointer: polynomial %u", i);
+        c.pin(polys[i], lens[i] * 32);
+        void* d = nullptr;
+        PLK_TRY(c.in(d, polys[i], lens[i] * 32));
+        dev[i] = d;
+    }
+    return PLK_OK;
+}
+int plk_plonk_eval_polys(int field, unsigned n_polys, const uint64_t* const* polys, const size_t* lens, unsigned n_points, const uint64_t* points, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    if (n_points < 1 || n_points > 8) return set_error(PLK_ERR_INVALID_ARG, "n_points %u is not in 1..8", n_points);
+    if (!points || (n_polys && (!polys || !lens || !out))) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    std::vector<const void*> dev;
+    PLK_TRY(lane_upload_polys(c, n_polys, polys, lens, dev));
+    void* dout = nullptr;
+    const size_t bytes = (size_t)n_polys * n_points * 32;
+    PLK_TRY(c.tmp(dout, bytes));
+    PLK_TRY(plonk_eval_polys_dev_impl(field, n_polys, dev.data(), lens, n_points, points, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, bytes));
+    return c.finish();
+}
+int plk_poly_reduce_dev(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, const uint64_t* scalars, size_t degree, void* d_out,
+                        void* stream) {
+    PLK_API;
+    return poly_reduce_dev_impl(field, n_polys, d_polys, lens, scalars, degree, d_out, as_stream(stream));
+}
+int plk_poly_reduce(int field, unsigned n_polys, const uint64_t* const* polys, const size_t* lens, const uint64_t* scalars, size_t degree, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    if ((n_polys && (!polys || !lens || !scalars)) || (degree && !out)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    for (unsigned i = 0; i < n_polys; ++i)
+        if (lens[i] > degree) return set_error(PLK_ERR_INVALID_ARG, "polynomial %u has %zu coefficients, more than the degree %zu (halo.rs:41)", i, lens[i], degree);
+    LaneCall c;
+    PLK_TRY(c.begin());
+    std::vector<const void*> dev;
+    PLK_TRY(lane_upload_polys(c, n_polys, polys, lens, dev));
+    c.pin(out, degree * 32);
+    void* dout = nullptr;
+    PLK_TRY(c.tmp(dout, degree * 32));
+    PLK_TRY(poly_reduce_dev_impl(field, n_polys, dev.data(), lens, scalars, degree, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, degree * 32));
+    return c.finish();
+}
+int plk_halo_build_b_dev(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, void* d_out, void* stream) {
+    PLK_API;
+    return halo_build_b_dev_impl(field, n_points, points, v, degree, d_out, as_stream(stream));
+}
+int plk_halo_build_b(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    if (n_points < 1 || n_points > 8) return set_error(PLK_ERR_INVALID_ARG, "n_points %u is not in 1..8", n_points);
+    if (!points || !v || (degree && !out)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(out, degree * 32);
+    void* dout = nullptr;
+    PLK_TRY(c.tmp(dout, degree * 32));
+    PLK_TRY(halo_build_b_dev_impl(field, n_points, points, v, degree, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, degree * 32));
+    return c.finish();
+}
+int plk_halo_s_dev(int field, unsigned k, const uint64_t* us, void* d_out, void* stream) {
+    PLK_API;
+    return halo_s_dev_impl(field, k, us, d_out, as_stream(stream));
+}
+int plk_halo_s(int field, unsigned k, const uint64_t* us, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    if (k > 30) return set_error(PLK_ERR_INVALID_ARG, "%u challenges: at most 30", k);
+    if ((k && !us) || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    for (unsigned j = 0; j < k; ++j)
+        if (!(us[4 * j] | us[4 * j + 1] | us[4 * j + 2] | us[4 * j + 3]))
+            return set_error(PLK_ERR_INVALID_ARG, "No inverse: challenge %u is zero (field.rs:266, from plonk_util.rs:314)", j);
+    const size_t bytes = ((size_t)1 << k) * 32;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(out, bytes);
+    void* dout = nullptr;
+    PLK_TRY(c.tmp(dout, bytes));
+    PLK_TRY(halo_s_dev_impl(field, k, us, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, bytes));
+    return c.finish();
+}
+
 // ---- MSM ----
 // Over a device group (plk_init_devices) a tabled precomputation of at least 2^PLK_MULTI_MIN_LOG_N generators is built on every
 // device (multi.hip); smaller ones, and table-free contexts (one-shot MSMs: latency, not throughput), stay on the caller's device.

@@ -146,6 +146,13 @@ int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* 
                                     const uint64_t* inner_a, void* d_out, hipStream_t stream);
 int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
                                  const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, hipStream_t stream);
+// the opening step (opening.hip): d_polys / lens are HOST arrays of n_polys device pointers / lengths, the scalars host limbs
+int plonk_eval_polys_dev_impl(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, unsigned n_points, const uint64_t* points, void* d_out,
+                              hipStream_t stream);
+int poly_reduce_dev_impl(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, const uint64_t* scalars, size_t degree, void* d_out,
+                         hipStream_t stream);
+int halo_build_b_dev_impl(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, void* d_out, hipStream_t stream);
+int halo_s_dev_impl(int field, unsigned k, const uint64_t* us, void* d_out, hipStream_t stream);
 int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_constants, const void* d_local, const void* d_right, const void* d_below,
                                    const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_out, hipStream_t stream);
 

@@ -212,6 +212,74 @@ def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k
     return (out, status) if want_status else out
 
 
+# ---- the opening step on device-resident polynomials (plonk.rs:261-308, halo.rs:38-44, 143-155) ----
+def _poly_list(polys):
+    """list of (len, 4) int64 CUDA tensors -> (ctypes array of device pointers, size_t lengths)"""
+    for t in polys:
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4
+    ptrs = (ctypes.c_void_p * max(1, len(polys)))(*[t.data_ptr() if t.shape[0] else None for t in polys])
+    lens = np.array([t.shape[0] for t in polys], dtype=np.uint64)
+    return ptrs, lens
+
+
+def _out_tensor(out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.int64, device=device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == tuple(shape)
+    return out
+
+
+def powers_dev(field, x, n, out=None, device="cuda"):
+    """powers (plonk_util.rs:123-133) -> (n, 4) int64 CUDA tensor; x: host limbs."""
+    out = _out_tensor(out, (n, 4), device)
+    xs = _limbs(x)
+    _lib.check(_lib.load().plk_field_powers_dev(field, xs.ctypes.data_as(ctypes.c_void_p), n, ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def eval_polys_dev(field, polys, points, out=None):
+    """open_all_polynomials (plonk.rs:459-482) for all points at once: polys a list of (len, 4) int64 CUDA tensors (any lengths, the
+    same tensor may appear twice), points (n_points, 4) host limbs, 1..8 points -> (n_points, n_polys, 4) CUDA tensor.  Every
+    polynomial is read once."""
+    ptrs, lens = _poly_list(polys)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    device = polys[0].device if polys else "cuda"
+    out = _out_tensor(out, (pts.shape[0], len(polys), 4), device)
+    _lib.check(_lib.load().plk_plonk_eval_polys_dev(field, len(polys), ptrs, lens.ctypes.data_as(ctypes.c_void_p), pts.shape[0],
+                                                    pts.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def reduce_polynomials_dev(field, polys, scalars, degree, out=None):
+    """reduced_coeffs (halo.rs:38-44), the argument's halo_a: sum_i scalars[i] * polys[i], zero-padded to `degree` -> (degree, 4)."""
+    ptrs, lens = _poly_list(polys)
+    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    assert sc.shape[0] == len(polys), "one scalar per polynomial"
+    device = polys[0].device if polys else "cuda"
+    out = _out_tensor(out, (degree, 4), device)
+    _lib.check(_lib.load().plk_poly_reduce_dev(field, len(polys), ptrs, lens.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), degree,
+                                               ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def build_halo_b_dev(field, points, v, degree, out=None, device="cuda"):
+    """build_halo_b (halo.rs:143-155), the argument's halo_b: out[j] = sum_k v^k points[k]^j -> (degree, 4)."""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    vs = _limbs(v)
+    out = _out_tensor(out, (degree, 4), device)
+    _lib.check(_lib.load().plk_halo_build_b_dev(field, pts.shape[0], pts.ctypes.data_as(ctypes.c_void_p), vs.ctypes.data_as(ctypes.c_void_p), degree,
+                                                ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def halo_s_dev(field, us, out=None, device="cuda"):
+    """halo_s (plonk_util.rs:311-326) -> (2^k, 4); us: (k, 4) host limbs, none of them zero."""
+    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    out = _out_tensor(out, (1 << u.shape[0], 4), device)
+    _lib.check(_lib.load().plk_halo_s_dev(field, u.shape[0], u.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
 # ---- one round of the inner-product argument (halo.rs:63-124) on device-resident vectors ----
 def _limbs(x, n=4):
     return np.ascontiguousarray(x, dtype=np.uint64).reshape(n)

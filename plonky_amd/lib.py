@@ -54,6 +54,16 @@ SYMBOLS = [
     ("plk_plonk_vanishing_points", _i, [_i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_permutation_z_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_permutation_z", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_field_powers_dev", _i, [_i, _vp, _sz, _vp, _vp]),
+    ("plk_field_powers", _i, [_i, _vp, _sz, _vp]),
+    ("plk_plonk_eval_polys_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp]),
+    ("plk_plonk_eval_polys", _i, [_i, _u, _vp, _vp, _u, _vp, _vp]),
+    ("plk_poly_reduce_dev", _i, [_i, _u, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("plk_poly_reduce", _i, [_i, _u, _vp, _vp, _vp, _sz, _vp]),
+    ("plk_halo_build_b_dev", _i, [_i, _u, _vp, _vp, _sz, _vp, _vp]),
+    ("plk_halo_build_b", _i, [_i, _u, _vp, _vp, _sz, _vp]),
+    ("plk_halo_s_dev", _i, [_i, _u, _vp, _vp, _vp]),
+    ("plk_halo_s", _i, [_i, _u, _vp, _vp]),
     ("plk_plonk_evaluate_all_constraints", _i, [_i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_msm_precompute", _i, [_i, _sz, _vp, _vp, _u, _vp]),
     ("plk_msm_precompute_dev", _i, [_i, _sz, _vp, _vp, _u, _vp, _vp]),

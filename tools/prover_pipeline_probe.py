@@ -128,8 +128,40 @@ if WITH_IPA:
     us = [synth.to_int(row) % r or 1 for row in synth.rand_field(F, 31, log_n)]
     ums = [(m1(u), m1(pow(u, -1, r))) for u in us]
     bl = [(m1(100 + j), m1(200 + j)) for j in range(log_n)]
+    # the opening (plonk.rs:261-308, halo.rs:38-47): the 30 polynomials - 6 constants, 6 sigmas, 9 wires, Z, 7 chunks of t, and the
+    # public-input quotient (a stand-in: the circuit has no public inputs) - at zeta, zeta g, zeta g^65; then halo_a, halo_b
     polys = dev.ntt_dev(F, wires, inverse=True)
-    halo_a, halo_b = polys[0].contiguous(), dev.to_device(synth.rand_field(F, 32, n))
+    sigma_coeffs = dev.ntt_dev(F, sigma_n, inverse=True)
+    zpoly = dev.ntt_dev(F, zvals, inverse=True)
+    opened = [const_coeffs[i] for i in range(6)] + [sigma_coeffs[i] for i in range(6)] + [polys[i] for i in range(9)] + [zpoly] + \
+             [t7[i * n:(i + 1) * n] for i in range(7)] + [dev.to_device(synth.rand_field(F, 33, n))]
+    assert len(opened) == 30
+    gsub = np.zeros((n, 4), dtype=np.uint64); gsub[1] = ONE
+    g_n = synth.from_mont(F, dev.to_host(dev.ntt_dev(F, dev.to_device(gsub))[1]))          # the generator of the n-subgroup
+    zeta_int = synth.to_int(synth.rand_field(F, 34, 1)[0]) % r
+    open_pts = np.stack([m1(zeta_int), m1(zeta_int * g_n % r), m1(zeta_int * pow(g_n, 65, r) % r)])
+    s_ints = [synth.to_int(row) % r for row in synth.rand_field(F, 35, 30)]                 # u^i: stand-in challenges
+    v_int = synth.to_int(synth.rand_field(F, 36, 1)[0]) % r
+    s_m = np.stack([m1(x) for x in s_ints])
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    for _ in range(2):
+        ev[0].record()
+        o = dev.eval_polys_dev(F, opened, open_pts)
+        ev[1].record()
+        halo_a = dev.reduce_polynomials_dev(F, opened, s_m, n)
+        ev[2].record()
+        halo_b = dev.build_halo_b_dev(F, open_pts, m1(v_int), n)
+        ev[3].record()
+    torch.cuda.synchronize()
+    open_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(3)]
+    for nm, tv in zip(("opening: 30 polys at 3 points", "opening: reduced polynomial halo_a", "opening: halo_b"), open_ms):
+        print("  %-34s %8.3f ms" % (nm, tv))
+    # <halo_a, halo_b> = sum_k v^k sum_i s_i o[k][i]: the identity that ties the three results together, checked on the device's outputs
+    o_int = [[synth.from_mont(F, row) for row in pt] for pt in dev.to_host(o)]
+    rhs = sum(pow(v_int, k, r) * sum(s * x for s, x in zip(s_ints, o_int[k])) for k in range(3)) % r
+    lhs = synth.from_mont(F, dev.to_host(dev.inner_product_dev(F, halo_a, halo_b))[0])
+    assert lhs == rhs, "<halo_a, halo_b> != sum_k v^k sum_i s_i o[k][i]"
+    print("  <halo_a, halo_b> == sum_k v^k sum_i s_i o[k][i]: True")
     g_only = gens[:n].contiguous()
     def ipa():
         t0 = time.perf_counter()
@@ -149,4 +181,4 @@ if WITH_IPA:
     ipa()
     t_ipa, _ = ipa()
     print("  %-34s %8.3f ms   (%d rounds over the same tables; wall clock of the loop, every round ends on the host)" % ("inner-product argument", t_ipa * 1e3, log_n))
-    print("hot path of one proof incl. the opening: %.2f ms" % (sum(ms) + t_ipa * 1e3))
+    print("hot path of one proof incl. the opening: %.2f ms" % (sum(ms) + sum(open_ms) + t_ipa * 1e3))
