@@ -166,6 +166,25 @@ int plk_poly_divide_by_z_h_dev(int field, const void* d_coeffs, size_t len, size
 int plk_poly_mul(int field, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* out, size_t out_cap, size_t* out_len);
 int plk_poly_mul_dev(int field, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t out_cap, size_t* out_len,
                      void* stream);
+/* Polynomial::polynomial_division (polynomial.rs:299-327; polynomial_long_division, polynomial.rs:232-259, gives the same) for a
+ * divisor of LOW degree: the public-input quotient of the prover (plonk.rs:199-235), whose divisor prod (X - s_i) has degree
+ * ceil(num_public_inputs / 9).  a = q b + rem, deg rem < deg b.  The reference inverts rev(b) mod X^n by Newton's iteration
+ * (inv_mod_xn: log n rounds of three transforms); here the division is the k-th order linear recurrence it is, scanned over segments
+ * of a (polydiv.hip).  Quotient and remainder are unique: the words are the reference's.
+ * d_a: la coefficients on the device; leading zero coefficients are allowed (they give leading zeros in q).  b: HOST array of lb
+ * coefficients (4 limbs each, Montgomery form, like the scalars of the opening step), b[lb - 1] != 0, degree k = lb - 1 with
+ * 1 <= k <= PLK_POLY_DIV_MAX_DEGREE, la > k; anything else is PLK_ERR_INVALID_ARG.  d_q: q_len >= la - k elements: the quotient
+ * followed by zeros (the reference's ans.pad(degree), plonk.rs:234: the prover passes q_len = n).  d_rem (nullable): k elements, the
+ * remainder zero-padded to k.  A divisor that is not monic is divided by its leading coefficient inside (one inversion on the host;
+ * none for a monic b, the prover's case).  Asynchronous on `stream`, no synchronisation, inputs unchanged, working memory from the
+ * library's scratch pool; d_q and d_rem must not overlap d_a (a is read twice).  Fields: the five 4-limb fields. */
+#define PLK_POLY_DIV_MAX_DEGREE 32
+int plk_poly_division_dev(int field, const void* d_a, size_t la, const uint64_t* b, size_t lb, void* d_q, size_t q_len, void* d_rem, void* stream);
+/* Same with host pointers for a, q and rem. */
+int plk_poly_division(int field, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* q, size_t q_len, uint64_t* rem);
+/* The fold of plonk.rs:207-215: out[0..k] = coefficients of prod_{i < k} (X - roots[i]), monic; k = 0 gives [1];
+ * k <= PLK_POLY_DIV_MAX_DEGREE.  Host pointers, computed on the host (at most k^2 / 2 products): no launch. */
+int plk_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out);
 
 /* ---- the Plonk quotient numerator  (src/plonk.rs, src/gates/) ------------------------------------ */
 /* The 8n-point loop of Prover::vanishing_poly (plonk.rs:392-453): for every point x = g^i of the 8n domain the

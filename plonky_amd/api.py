@@ -183,6 +183,66 @@ def polynomial_mul(field, a, b):
     return out[: out_len.value].copy()
 
 
+POLY_DIV_MAX_DEGREE = 32  # PLK_POLY_DIV_MAX_DEGREE
+
+
+def _degree_plus_one(x):
+    """Polynomial::degree_plus_one (polynomial.rs:107-112): 0 for the zero polynomial"""
+    nz = np.nonzero(x.any(axis=1))[0]
+    return int(nz[-1]) + 1 if nz.size else 0
+
+
+def polynomial_division(field, a, b):
+    """Polynomial::polynomial_division (polynomial.rs:299-327) -> (q, r) with the reference's lengths in every branch: a zero a gives
+    ([0], empty), deg a < deg b gives ([0], a), deg b = 0 gives a / b[0] untrimmed and an empty remainder, otherwise q and r trimmed.
+    A zero b raises (the reference panics); a divisor of degree above 32 raises ValueError: the device divides by the linear recurrence
+    that a LOW-degree divisor gives (plk_poly_division), the divisor of the public-input quotient (plonk.rs:199-235)."""
+    x, y = _elems(field, a), _elems(field, b)
+    da, db = _degree_plus_one(x), _degree_plus_one(y)
+    empty = np.zeros((0, 4), dtype=np.uint64)
+    if db == 0:
+        raise ZeroDivisionError("Division by zero polynomial")
+    if da == 0:
+        return np.zeros((1, 4), dtype=np.uint64), empty
+    if da < db:
+        return np.zeros((1, 4), dtype=np.uint64), x.copy()
+    if db == 1:
+        inv = field_op(field, "inverse", y[:1])
+        return field_op(field, "mul", x, np.repeat(inv, x.shape[0], axis=0)), empty
+    if db - 1 > POLY_DIV_MAX_DEGREE:
+        raise ValueError("divisor of degree %d: at most %d (PLK_POLY_DIV_MAX_DEGREE)" % (db - 1, POLY_DIV_MAX_DEGREE))
+    xs, ys = np.ascontiguousarray(x[:da]), np.ascontiguousarray(y[:db])
+    q = np.empty((da - db + 1, 4), dtype=np.uint64)
+    r = np.empty((db - 1, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_poly_division(field, _ptr(xs), da, _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
+    return q, r[: _degree_plus_one(r)].copy()
+
+
+def polynomial_long_division(field, a, b):
+    """Polynomial::polynomial_long_division (polynomial.rs:232-259): the same quotient and remainder; its deg b = 0 case goes through
+    the loop and leaves the quotient at deg a + 1 coefficients."""
+    x, y = _elems(field, a), _elems(field, b)
+    if _degree_plus_one(y) == 1 and _degree_plus_one(x) >= 1:
+        q, r = polynomial_division(field, x[: _degree_plus_one(x)], y)
+        return q, r
+    return polynomial_division(field, a, b)
+
+
+def polynomial_from_roots(field, roots):
+    """prod_i (X - roots[i]) (the fold of plonk.rs:207-215) -> (k + 1, 4), monic; at most 32 roots."""
+    r = np.ascontiguousarray(roots, dtype=np.uint64).reshape(-1, 4)
+    out = np.empty((r.shape[0] + 1, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_poly_from_roots(field, r.shape[0], _ptr(r), _ptr(out)))
+    return out
+
+
+def scale_polynomials(field, polys, alpha, degree):
+    """scale_polynomials (plonk_util.rs:283-298): sum_j alpha^j polys[j], the first `degree` coefficients: powers + reduce_polynomials."""
+    polys = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+    assert all(p.shape[0] >= degree for p in polys), "the reference indexes every polynomial up to degree"
+    return reduce_polynomials(field, [p[:degree] for p in polys], powers(field, alpha, len(polys)), degree)
+
+
 def polynomials_to_values_padded(polys, precomputation):
     """plonk_util.rs:179-190: every polynomial padded to 8x its length, then evaluated on the
     precomputation's domain (eval_domain pads further when the domain is larger).  polys: sequence of

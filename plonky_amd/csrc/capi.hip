@@ -715,6 +715,34 @@ int plk_poly_mul(int field, const uint64_t* a, size_t la, const uint64_t* b, siz
     return c.finish();
 }
 
+// ---- low-degree polynomial division: the public-input quotient (polydiv.hip) ----
+int plk_poly_division_dev(int field, const void* d_a, size_t la, const uint64_t* b, size_t lb, void* d_q, size_t q_len, void* d_rem, void* stream) {
+    PLK_API;
+    return poly_division_dev_impl(field, d_a, la, b, lb, d_q, q_len, d_rem, as_stream(stream));
+}
+int plk_poly_division(int field, const uint64_t* a, size_t la, const uint64_t* b, size_t lb, uint64_t* q, size_t q_len, uint64_t* rem) {
+    PLK_API;
+    PLK_TRY(poly_division_check(field, la, b, lb, q_len));
+    if (!a || !q) return set_error(PLK_ERR_INVALID_ARG, "null pointer: a / q");
+    const size_t k = lb - 1;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(a, la * 32);
+    c.pin(q, q_len * 32);
+    void *da = nullptr, *dq = nullptr, *drem = nullptr;
+    PLK_TRY(c.in(da, a, la * 32));
+    PLK_TRY(c.tmp(dq, q_len * 32));
+    PLK_TRY(c.tmp(drem, k * 32));
+    PLK_TRY(poly_division_dev_impl(field, da, la, b, lb, dq, q_len, drem, c.stream()));
+    PLK_TRY(c.out(q, dq, q_len * 32));
+    if (rem) PLK_TRY(c.out(rem, drem, k * 32));
+    return c.finish();
+}
+int plk_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out) {
+    PLK_API;
+    return poly_from_roots_impl(field, k, roots, out);
+}
+
 // ---- the Plonk quotient numerator ----
 int plk_plonk_vanishing_points_dev(int field, unsigned log_degree, const void* d_constants_8n, const void* d_wires_8n, const void* d_s_sigma_8n,
                                    const void* d_plonk_z_8n, const uint64_t* k_is, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,

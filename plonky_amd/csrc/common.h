@@ -8,6 +8,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/plonky_hip.h"
 
@@ -98,6 +99,22 @@ void* scratch_acquire(size_t bytes, hipStream_t stream);  // nullptr on allocati
 void scratch_release(void* p, hipStream_t stream);       // call after the last kernel using p is enqueued
 void scratch_clear();
 
+struct ScratchSet {  // scratch buffers of one call (opening.hip, polydiv.hip), released in stream order on every exit path
+    hipStream_t stream;
+    std::vector<void*> bufs;
+    explicit ScratchSet(hipStream_t s) : stream(s) {}
+    ScratchSet(const ScratchSet&) = delete;
+    ScratchSet& operator=(const ScratchSet&) = delete;
+    void* get(size_t bytes) {
+        void* p = scratch_acquire(bytes ? bytes : 16, stream);
+        if (p) bufs.push_back(p);
+        return p;
+    }
+    ~ScratchSet() {
+        for (void* p : bufs) scratch_release(p, stream);
+    }
+};
+
 // Streams of the library's own (side streams of a context, the lanes of the host-pointer entry points) come from a process-wide
 // pool and go back to it instead of being destroyed: events of the scratch pool (and of other contexts) may have been recorded on
 // them last, and HIP keeps a pointer to the recording stream in an event - querying or waiting on such an event after
@@ -153,6 +170,10 @@ int poly_reduce_dev_impl(int field, unsigned n_polys, const void* const* d_polys
                          hipStream_t stream);
 int halo_build_b_dev_impl(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, void* d_out, hipStream_t stream);
 int halo_s_dev_impl(int field, unsigned k, const uint64_t* us, void* d_out, hipStream_t stream);
+// low-degree polynomial division (polydiv.hip): b is a HOST array of lb coefficients
+int poly_division_check(int field, size_t la, const uint64_t* b, size_t lb, size_t q_len);
+int poly_division_dev_impl(int field, const void* d_a, size_t la, const uint64_t* b, size_t lb, void* d_q, size_t q_len, void* d_rem, hipStream_t stream);
+int poly_from_roots_impl(int field, unsigned k, const uint64_t* roots, uint64_t* out);
 int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_constants, const void* d_local, const void* d_right, const void* d_below,
                                    const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_out, hipStream_t stream);
 

@@ -280,22 +280,6 @@ static void put_words8(uint32_t* dst, const uint64_t* src) {
     }
 }
 
-struct ScratchSet {  // scratch buffers of one call, released in stream order on every exit path
-    hipStream_t stream;
-    std::vector<void*> bufs;
-    explicit ScratchSet(hipStream_t s) : stream(s) {}
-    ScratchSet(const ScratchSet&) = delete;
-    ScratchSet& operator=(const ScratchSet&) = delete;
-    void* get(size_t bytes) {
-        void* p = scratch_acquire(bytes ? bytes : 16, stream);
-        if (p) bufs.push_back(p);
-        return p;
-    }
-    ~ScratchSet() {
-        for (void* p : bufs) scratch_release(p, stream);
-    }
-};
-
 static int check_polys(unsigned n_polys, const void* const* d_polys, const size_t* lens) {
     if (n_polys && (!d_polys || !lens)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     for (unsigned i = 0; i < n_polys; ++i)

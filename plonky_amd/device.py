@@ -280,6 +280,33 @@ def halo_s_dev(field, us, out=None, device="cuda"):
     return out
 
 
+# ---- the public-input quotient (plonk.rs:199-235): low-degree polynomial division on device-resident coefficients ----
+def polynomial_division_dev(field, a, b, q_len=None, out=None, rem=None):
+    """plk_poly_division_dev: a (la, 4) int64 CUDA tensor, b (lb, 4) host limbs with b[lb - 1] != 0 and 1 <= lb - 1 <= 32 < la ->
+    (q, rem): q (q_len, 4), the quotient followed by zeros (q_len defaults to la - k), rem (k, 4).  Nothing is synchronised."""
+    assert a.is_cuda and a.dtype == torch.int64 and a.is_contiguous() and a.dim() == 2 and a.shape[1] == 4
+    bs = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+    la, k = a.shape[0], bs.shape[0] - 1
+    if q_len is None:
+        q_len = out.shape[0] if out is not None else max(la - k, 0)
+    out = _out_tensor(out, (q_len, 4), a.device)
+    rem = _out_tensor(rem, (max(k, 0), 4), a.device)
+    _lib.check(_lib.load().plk_poly_division_dev(field, ctypes.c_void_p(a.data_ptr()), la, bs.ctypes.data_as(ctypes.c_void_p), bs.shape[0],
+                                                 ctypes.c_void_p(out.data_ptr()), q_len, ctypes.c_void_p(rem.data_ptr()), _stream()))
+    return out, rem
+
+
+def public_input_quotient_dev(field, wire_polys_no_pis, alpha, roots, degree):
+    """The public-input quotient of plonk.rs:199-235: scale_polynomials(wire polynomials without public inputs, alpha, degree) divided
+    by prod (X - roots[i]) over the public-input rows -> (quotient padded to `degree`, remainder (k, 4): zero for a valid witness).
+    api.powers (the nine powers of alpha, host scalars: a call on the library's own lane) + reduce_polynomials_dev + plk_poly_from_roots + the
+    division; the polynomials stay on the device and the caller's stream is never synchronised."""
+    from .api import polynomial_from_roots, powers
+    pw = powers(field, alpha, len(wire_polys_no_pis))  # host scalars of the reduction: the caller's stream is not touched
+    scaled = reduce_polynomials_dev(field, [p[:degree] for p in wire_polys_no_pis], pw, degree)
+    return polynomial_division_dev(field, scaled, polynomial_from_roots(field, roots), q_len=degree)
+
+
 # ---- one round of the inner-product argument (halo.rs:63-124) on device-resident vectors ----
 def _limbs(x, n=4):
     return np.ascontiguousarray(x, dtype=np.uint64).reshape(n)

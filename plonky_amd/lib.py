@@ -50,6 +50,9 @@ SYMBOLS = [
     ("plk_poly_divide_by_z_h_dev", _i, [_i, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
     ("plk_poly_mul", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     ("plk_poly_mul_dev", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("plk_poly_division_dev", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("plk_poly_division", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    ("plk_poly_from_roots", _i, [_i, _u, _vp, _vp]),
     ("plk_plonk_vanishing_points_dev", _i, [_i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_vanishing_points", _i, [_i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_permutation_z_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -129,15 +129,32 @@ if WITH_IPA:
     ums = [(m1(u), m1(pow(u, -1, r))) for u in us]
     bl = [(m1(100 + j), m1(200 + j)) for j in range(log_n)]
     # the opening (plonk.rs:261-308, halo.rs:38-47): the 30 polynomials - 6 constants, 6 sigmas, 9 wires, Z, 7 chunks of t, and the
-    # public-input quotient (a stand-in: the circuit has no public inputs) - at zeta, zeta g, zeta g^65; then halo_a, halo_b
+    # public-input quotient (plonk.rs:199-235, k = 2 public-input rows) - at zeta, zeta g, zeta g^65; then halo_a, halo_b
     polys = dev.ntt_dev(F, wires, inverse=True)
     sigma_coeffs = dev.ntt_dev(F, sigma_n, inverse=True)
     zpoly = dev.ntt_dev(F, zvals, inverse=True)
     opened = [const_coeffs[i] for i in range(6)] + [sigma_coeffs[i] for i in range(6)] + [polys[i] for i in range(9)] + [zpoly] + \
-             [t7[i * n:(i + 1) * n] for i in range(7)] + [dev.to_device(synth.rand_field(F, 33, n))]
-    assert len(opened) == 30
+             [t7[i * n:(i + 1) * n] for i in range(7)]
     gsub = np.zeros((n, 4), dtype=np.uint64); gsub[1] = ONE
     g_n = synth.from_mont(F, dev.to_host(dev.ntt_dev(F, dev.to_device(gsub))[1]))          # the generator of the n-subgroup
+    # the wire values without public inputs are zero at the public-input rows (plonk.rs:109-118): rows 0 and 1 here, the subgroup
+    # points 1 and g; their polynomials, scaled by powers of alpha, divided by (X - 1)(X - g) (plonk.rs:199-235)
+    PI_ROWS = 2
+    wires_no_pis = wires.clone()
+    wires_no_pis[:, :PI_ROWS] = 0
+    polys_no_pis = dev.ntt_dev(F, wires_no_pis, inverse=True)
+    pi_roots = np.stack([m1(pow(g_n, i, r)) for i in range(PI_ROWS)])
+    pe = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for _ in range(2):
+        pe[0].record()
+        pi_quotient, pi_rem = dev.public_input_quotient_dev(F, [polys_no_pis[i] for i in range(9)], alpha, pi_roots, n)
+        pe[1].record()
+    torch.cuda.synchronize()
+    pi_ok = bool(not dev.to_host(pi_rem).any() and dev.to_host(pi_quotient).any())
+    print("  %-34s %8.3f ms   remainder is zero: %s" % ("public-input quotient (k = %d)" % PI_ROWS, pe[0].elapsed_time(pe[1]), pi_ok))
+    assert pi_ok, "the public-input quotient left a remainder"
+    opened.append(pi_quotient)
+    assert len(opened) == 30
     zeta_int = synth.to_int(synth.rand_field(F, 34, 1)[0]) % r
     open_pts = np.stack([m1(zeta_int), m1(zeta_int * g_n % r), m1(zeta_int * pow(g_n, 65, r) % r)])
     s_ints = [synth.to_int(row) % r for row in synth.rand_field(F, 35, 30)]                 # u^i: stand-in challenges
