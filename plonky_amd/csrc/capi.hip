@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ec.cuh"
 #include "host_lane.h"
 
 struct plk_msm_ctx;
@@ -365,36 +366,18 @@ void pin_registry_release(const void* ptr) {
     g_pin_cv.notify_all();
 }
 
+static int or_invalid_id(int rc) { return rc == PLK_NO_MATCH ? PLK_ERR_INVALID_ARG : rc; }
 int field_limbs(int field) {
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE:
-        case PLK_FIELD_TWEEDLEDUM_BASE:
-        case PLK_FIELD_BLS12_377_SCALAR:
-        case PLK_FIELD_PALLAS_BASE:
-        case PLK_FIELD_VESTA_BASE: return 4;
-        case PLK_FIELD_BLS12_377_BASE: return 6;
-    }
-    return PLK_ERR_INVALID_ARG;
+    return or_invalid_id(with_field(field, [](auto t) { return tag_t<decltype(t)>::NL / 2; }));
 }
 int curve_limbs(int curve) {
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE:
-        case PLK_CURVE_TWEEDLEDUM:
-        case PLK_CURVE_PALLAS:
-        case PLK_CURVE_VESTA: return 4;
-        case PLK_CURVE_BLS12_377: return 6;
-    }
-    return PLK_ERR_INVALID_ARG;
+    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::FP::NL / 2; }));
 }
 int curve_scalar_field(int curve) {
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return PLK_FIELD_TWEEDLEDUM_BASE;
-        case PLK_CURVE_TWEEDLEDUM: return PLK_FIELD_TWEEDLEDEE_BASE;
-        case PLK_CURVE_BLS12_377: return PLK_FIELD_BLS12_377_SCALAR;
-        case PLK_CURVE_PALLAS: return PLK_FIELD_VESTA_BASE;
-        case PLK_CURVE_VESTA: return PLK_FIELD_PALLAS_BASE;
-    }
-    return PLK_ERR_INVALID_ARG;
+    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::SP::FIELD_ID; }));
+}
+int curve_scalar_bits(int curve) {
+    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::SP::BITS; }));
 }
 
 }  // namespace plk

@@ -242,10 +242,9 @@ __global__ void __launch_bounds__(COMB_RED_THREADS) k_comb_reduce(const uint4* _
 }
 
 // ---- host side ----
-static int comb_scalar_bits(int curve) { return curve == PLK_CURVE_BLS12_377 ? 253 : 255; }
 
 size_t comb_table_bytes(int curve, size_t n) {
-    const int windows = (comb_scalar_bits(curve) + 1 + COMB_C - 1) / COMB_C;
+    const int windows = (curve_scalar_bits(curve) + 1 + COMB_C - 1) / COMB_C;
     return n * (size_t)windows * COMB_MULT * (size_t)2 * curve_limbs(curve) * 8 + 16;
 }
 
@@ -277,7 +276,7 @@ int comb_build(int curve, size_t n, const void* d_base0, const void* d_chain, hi
     CombPlan* p = new CombPlan();
     p->curve = curve;
     p->n = n;
-    p->windows = (comb_scalar_bits(curve) + 1 + COMB_C - 1) / COMB_C;
+    p->windows = (curve_scalar_bits(curve) + 1 + COMB_C - 1) / COMB_C;
     p->groups = (p->windows + COMB_WPL - 1) / COMB_WPL;
     (void)hipGetDevice(&p->device);
     p->tab_bytes = comb_table_bytes(curve, n);
@@ -285,14 +284,7 @@ int comb_build(int curve, size_t n, const void* d_base0, const void* d_chain, hi
         delete p;
         return set_error(PLK_ERR_OOM, "comb table of %zu bytes", comb_table_bytes(curve, n));
     }
-    int rc;
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: rc = comb_build_t<TweedledeeCurve>(p, d_base0, d_chain, stream); break;
-        case PLK_CURVE_TWEEDLEDUM: rc = comb_build_t<TweedledumCurve>(p, d_base0, d_chain, stream); break;
-        case PLK_CURVE_PALLAS: rc = comb_build_t<PallasCurve>(p, d_base0, d_chain, stream); break;
-        case PLK_CURVE_VESTA: rc = comb_build_t<VestaCurve>(p, d_base0, d_chain, stream); break;
-        default: rc = comb_build_t<Bls12377Curve>(p, d_base0, d_chain, stream); break;
-    }
+    const int rc = or_bad_curve(with_curve(curve, [&](auto t) { return comb_build_t<tag_t<decltype(t)>>(p, d_base0, d_chain, stream); }), curve);
     if (rc != PLK_OK) {
         (void)hipFree(p->tab);
         delete p;
@@ -342,15 +334,7 @@ int comb_execute(const CombPlan* p, unsigned batch, const void* const* d_scalars
             cb.v[k].out_zero = (uint8_t*)d_out_zero + b;
             if (count[b] > max_count) max_count = count[b];
         }
-        int rc;
-        switch (p->curve) {
-            case PLK_CURVE_TWEEDLEDEE: rc = comb_execute_t<TweedledeeCurve>(p, cb, max_count, stream); break;
-            case PLK_CURVE_TWEEDLEDUM: rc = comb_execute_t<TweedledumCurve>(p, cb, max_count, stream); break;
-            case PLK_CURVE_PALLAS: rc = comb_execute_t<PallasCurve>(p, cb, max_count, stream); break;
-            case PLK_CURVE_VESTA: rc = comb_execute_t<VestaCurve>(p, cb, max_count, stream); break;
-            default: rc = comb_execute_t<Bls12377Curve>(p, cb, max_count, stream); break;
-        }
-        PLK_TRY(rc);
+        PLK_TRY(or_bad_curve(with_curve(p->curve, [&](auto t) { return comb_execute_t<tag_t<decltype(t)>>(p, cb, max_count, stream); }), p->curve));
     }
     return PLK_OK;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/plonky_hip.h"
+#include "dispatch.cuh"
 
 namespace plk {
 
@@ -31,6 +32,20 @@ int set_error(int code, const char* fmt, ...);
         int _rc = (expr);          \
         if (_rc != PLK_OK) return _rc; \
     } while (0)
+
+// what with_field / with_curve (dispatch.cuh, ec.cuh) return for an id outside their list, as the call site's PLK_ERR_INVALID_ARG text
+// (fmt takes the id); any other rc passes
+inline int or_invalid(int rc, const char* fmt, int id) { return rc == PLK_NO_MATCH ? set_error(PLK_ERR_INVALID_ARG, fmt, id) : rc; }
+inline int or_bad_field(int rc, int field) { return or_invalid(rc, "bad field id %d", field); }
+inline int or_bad_curve(int rc, int curve) { return or_invalid(rc, "bad curve id %d", curve); }
+
+// n 64-bit limbs (the C ABI's form of a field element) as 2n 32-bit words (the kernels' form), little-endian
+inline void limbs_to_words(uint32_t* words, const uint64_t* limbs, int n = 4) {
+    for (int k = 0; k < n; ++k) {
+        words[2 * k] = (uint32_t)limbs[k];
+        words[2 * k + 1] = (uint32_t)(limbs[k] >> 32);
+    }
+}
 
 // Makes sure the calling thread's device is selected (plk_init may have been called on another thread: hipSetDevice is per
 // thread): the physical device of the thread's logical device in the group (multi.hip).
@@ -187,8 +202,10 @@ struct MsmParts {
     const uint32_t* bucket_parts = nullptr;  // (absent, 0 or 1: every bucket)
 };
 
-int field_limbs(int field);
-int curve_limbs(int curve);
-int curve_scalar_field(int curve);
+// properties of an id, read from the parameter structs through the dispatchers (capi.hip); PLK_ERR_INVALID_ARG for an unknown id
+int field_limbs(int field);         // 64-bit limbs of an element
+int curve_limbs(int curve);         // ... of a coordinate
+int curve_scalar_field(int curve);  // PLK_FIELD_* of the scalars
+int curve_scalar_bits(int curve);   // bits of the scalar field's modulus
 
 }  // namespace plk

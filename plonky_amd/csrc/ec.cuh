@@ -14,6 +14,7 @@
 // handled: identity operands, P + P (falls to doubling), P + (-P) (identity); 2-torsion points
 // (y = 0, possible on BLS12-377 G1 whose cofactor is even) double to the identity.
 #pragma once
+#include "dispatch.cuh"
 #include "fp.cuh"
 #include "glv_params.cuh"
 
@@ -50,6 +51,20 @@ struct VestaCurve {
     using SP = PallasBaseParams;
     using Glv = VestaGlv;
 };
+
+// From a run-time PLK_CURVE_* id to code instantiated on the curve struct (dispatch.cuh has the fields' twin and the protocol):
+// the one list of the curves, in the order of their ids.
+#define PLK_FOR_EACH_CURVE(X) X(TweedledeeCurve) X(TweedledumCurve) X(Bls12377Curve) X(PallasCurve) X(VestaCurve)
+
+template <class F> int with_curve(int curve, F&& f) {
+#define PLK_CURVE_CASE(C) \
+    if (curve == C::CURVE_ID) return f(TypeTag<C>{});
+    PLK_FOR_EACH_CURVE(PLK_CURVE_CASE)
+#undef PLK_CURVE_CASE
+    return PLK_NO_MATCH;
+}
+
+#ifdef __HIPCC__  // the group law is device code; the curve structs and with_curve above also serve plain C++ (hostnorm.cpp)
 
 template <class FP> struct Xyzz {
     Fe<FP> x, y, zz, zzz;
@@ -218,5 +233,7 @@ template <class FP> PLK_DI Xyzz<FP> xyzz_load(const uint4* src) {
     p.zzz = fe_load<FP>(src + 3 * W);
     return p;
 }
+
+#endif  // __HIPCC__
 
 }  // namespace plk

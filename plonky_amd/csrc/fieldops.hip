@@ -2,6 +2,7 @@
 // the reference's `test_arithmetic!` sweep (src/field/field.rs:618-780) so that the parity
 // tests can run the HIP field arithmetic itself against the oracle on the edge-value inputs.
 #include "common.h"
+#include "ec.cuh"
 #include "fp.cuh"
 #include "fz.cuh"
 
@@ -180,18 +181,10 @@ int field_batch_inverse_dev_impl(int field, const void* d_x, void* d_out, void* 
     if (!d_x || !d_out) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
     const unsigned blocks = batch_blocks(count);
-    switch (field) {
-#define CASE(ID, P) \
-    case ID: k_batch_inverse<P><<<blocks, 128, 0, stream>>>((const uint4*)d_x, (uint4*)d_out, (uint8_t*)d_is_zero, d_zero_count, count); break;
-        CASE(PLK_FIELD_TWEEDLEDEE_BASE, TweedledeeBaseParams)
-        CASE(PLK_FIELD_TWEEDLEDUM_BASE, TweedledumBaseParams)
-        CASE(PLK_FIELD_BLS12_377_SCALAR, Bls12377ScalarParams)
-        CASE(PLK_FIELD_BLS12_377_BASE, Bls12377BaseParams)
-        CASE(PLK_FIELD_PALLAS_BASE, PallasBaseParams)
-        CASE(PLK_FIELD_VESTA_BASE, VestaBaseParams)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
-    }
+    PLK_TRY(or_bad_field(with_field(field, [&](auto t) {
+        k_batch_inverse<tag_t<decltype(t)>><<<blocks, 128, 0, stream>>>((const uint4*)d_x, (uint4*)d_out, (uint8_t*)d_is_zero, d_zero_count, count);
+        return PLK_OK;
+    }), field));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -201,17 +194,11 @@ int curve_batch_to_affine_dev_impl(int curve, size_t count, const void* d_xyz, c
     if (!d_xyz || !d_out_xy || !d_out_zero) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
     const unsigned blocks = batch_blocks(count);
-    switch (curve) {
-#define CASE(ID, P) \
-    case ID: k_batch_to_affine<P><<<blocks, 128, 0, stream>>>((const uint4*)d_xyz, (const uint8_t*)d_zero, (uint4*)d_out_xy, (uint8_t*)d_out_zero, count); break;
-        CASE(PLK_CURVE_TWEEDLEDEE, TweedledeeBaseParams)
-        CASE(PLK_CURVE_TWEEDLEDUM, TweedledumBaseParams)
-        CASE(PLK_CURVE_BLS12_377, Bls12377BaseParams)
-        CASE(PLK_CURVE_PALLAS, PallasBaseParams)
-        CASE(PLK_CURVE_VESTA, VestaBaseParams)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using P = typename tag_t<decltype(t)>::FP;
+        k_batch_to_affine<P><<<blocks, 128, 0, stream>>>((const uint4*)d_xyz, (const uint8_t*)d_zero, (uint4*)d_out_xy, (uint8_t*)d_out_zero, count);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -275,31 +262,20 @@ __global__ void __launch_bounds__(256) k_fold_slices(const uint4* __restrict__ l
 int field_inner_product_dev_impl(int field, const void* d_a, const void* d_b, size_t count, void* d_out, hipStream_t stream) {
     if (!d_out || (count && (!d_a || !d_b))) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
-    const int L = field_limbs(field);
-    if (L < 0) return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
     unsigned blocks = (unsigned)((count + 255) / 256);
     if (blocks > 1024) blocks = 1024;
     if (blocks == 0) blocks = 1;
-    void* part = scratch_acquire((size_t)blocks * L * 8, stream);
-    if (!part) return PLK_ERR_OOM;
-    switch (field) {
-#define CASE(ID, P)                                                                                                   \
-    case ID:                                                                                                          \
-        k_inner_product<P><<<blocks, 256, 0, stream>>>((const uint4*)d_a, (const uint4*)d_b, count, (uint4*)part);   \
-        k_sum_parts<P><<<1, 256, 0, stream>>>((const uint4*)part, blocks, (uint4*)d_out);                            \
-        break;
-        CASE(PLK_FIELD_TWEEDLEDEE_BASE, TweedledeeBaseParams)
-        CASE(PLK_FIELD_TWEEDLEDUM_BASE, TweedledumBaseParams)
-        CASE(PLK_FIELD_BLS12_377_SCALAR, Bls12377ScalarParams)
-        CASE(PLK_FIELD_BLS12_377_BASE, Bls12377BaseParams)
-        CASE(PLK_FIELD_PALLAS_BASE, PallasBaseParams)
-        CASE(PLK_FIELD_VESTA_BASE, VestaBaseParams)
-#undef CASE
-    }
-    hipError_t e = hipGetLastError();
-    scratch_release(part, stream);
-    if (e != hipSuccess) return set_error(PLK_ERR_HIP, "inner product launch failed: %s", hipGetErrorString(e));
-    return PLK_OK;
+    return or_bad_field(with_field(field, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        void* part = scratch_acquire((size_t)blocks * P::NL * 4, stream);
+        if (!part) return PLK_ERR_OOM;
+        k_inner_product<P><<<blocks, 256, 0, stream>>>((const uint4*)d_a, (const uint4*)d_b, count, (uint4*)part);
+        k_sum_parts<P><<<1, 256, 0, stream>>>((const uint4*)part, blocks, (uint4*)d_out);
+        hipError_t e = hipGetLastError();
+        scratch_release(part, stream);
+        if (e != hipSuccess) return set_error(PLK_ERR_HIP, "inner product launch failed: %s", hipGetErrorString(e));
+        return PLK_OK;
+    }), field);
 }
 
 int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, const uint64_t* s_lo, const uint64_t* s_hi, size_t count, void* d_out,
@@ -307,27 +283,15 @@ int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, co
     if (count == 0) return PLK_OK;
     if (!d_lo || !d_hi || !d_out || !s_lo || !s_hi) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     PLK_TRY(ensure_device());
-    const int L = field_limbs(field);
-    if (L < 0) return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
-    FoldScalars sc;
-    for (int k = 0; k < L; ++k) {
-        sc.lo[2 * k] = (uint32_t)s_lo[k];
-        sc.lo[2 * k + 1] = (uint32_t)(s_lo[k] >> 32);
-        sc.hi[2 * k] = (uint32_t)s_hi[k];
-        sc.hi[2 * k + 1] = (uint32_t)(s_hi[k] >> 32);
-    }
     const unsigned blocks = (unsigned)((count + 255) / 256);
-    switch (field) {
-#define CASE(ID, P) \
-    case ID: k_fold_slices<P><<<blocks, 256, 0, stream>>>((const uint4*)d_lo, (const uint4*)d_hi, sc, count, (uint4*)d_out); break;
-        CASE(PLK_FIELD_TWEEDLEDEE_BASE, TweedledeeBaseParams)
-        CASE(PLK_FIELD_TWEEDLEDUM_BASE, TweedledumBaseParams)
-        CASE(PLK_FIELD_BLS12_377_SCALAR, Bls12377ScalarParams)
-        CASE(PLK_FIELD_BLS12_377_BASE, Bls12377BaseParams)
-        CASE(PLK_FIELD_PALLAS_BASE, PallasBaseParams)
-        CASE(PLK_FIELD_VESTA_BASE, VestaBaseParams)
-#undef CASE
-    }
+    PLK_TRY(or_bad_field(with_field(field, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        FoldScalars sc;
+        limbs_to_words(sc.lo, s_lo, P::NL / 2);
+        limbs_to_words(sc.hi, s_hi, P::NL / 2);
+        k_fold_slices<P><<<blocks, 256, 0, stream>>>((const uint4*)d_lo, (const uint4*)d_hi, sc, count, (uint4*)d_out);
+        return PLK_OK;
+    }), field));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -336,15 +300,7 @@ int field_op_impl(int field, int op, const uint64_t* a, const uint64_t* b, uint6
     if (op < 0 || op > 13) return set_error(PLK_ERR_INVALID_ARG, "bad field op %d", op);
     if (!a || !out || ((op <= 2 || op >= 12) && !b)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     PLK_TRY(ensure_device());
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return field_op_t<TweedledeeBaseParams>(op, a, b, out, count);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return field_op_t<TweedledumBaseParams>(op, a, b, out, count);
-        case PLK_FIELD_BLS12_377_SCALAR: return field_op_t<Bls12377ScalarParams>(op, a, b, out, count);
-        case PLK_FIELD_BLS12_377_BASE: return field_op_t<Bls12377BaseParams>(op, a, b, out, count);
-        case PLK_FIELD_PALLAS_BASE: return field_op_t<PallasBaseParams>(op, a, b, out, count);
-        case PLK_FIELD_VESTA_BASE: return field_op_t<VestaBaseParams>(op, a, b, out, count);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
+    return or_bad_field(with_field(field, [&](auto t) { return field_op_t<tag_t<decltype(t)>>(op, a, b, out, count); }), field);
 }
 
 }  // namespace plk

@@ -463,14 +463,8 @@ int curve_fold_multi_dev_impl(int curve, size_t n_out, int r_bits, const void* d
     if (n_out == 0) return PLK_OK;
     if (!d_g || !d_ratios || !d_out_xy || !d_out_zero) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return fold_multi_t<TweedledeeCurve>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_TWEEDLEDUM: return fold_multi_t<TweedledumCurve>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_BLS12_377: return fold_multi_t<Bls12377Curve>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_PALLAS: return fold_multi_t<PallasCurve>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_VESTA: return fold_multi_t<VestaCurve>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
+    return or_bad_curve(with_curve(curve, [&](auto t) { return fold_multi_t<tag_t<decltype(t)>>(n_out, r_bits, d_g, d_gz, d_ratios, d_out_xy, d_out_zero, stream); }),
+                        curve);
 }
 
 template <class C>
@@ -479,11 +473,9 @@ static int fold_pairs_t(size_t m, const void* d_lo, const void* d_lo_zero, const
     static_assert(C::SP::NL == 8, "scalar fields are 256-bit");
     if (m == 0) return PLK_OK;
     ScalarPair sp{};
-    for (int i = 0; i < 4 && !d_scalars; ++i) {
-        sp.a[2 * i] = (uint32_t)a_mont[i];
-        sp.a[2 * i + 1] = (uint32_t)(a_mont[i] >> 32);
-        sp.b[2 * i] = (uint32_t)b_mont[i];
-        sp.b[2 * i + 1] = (uint32_t)(b_mont[i] >> 32);
+    if (!d_scalars) {
+        limbs_to_words(sp.a, a_mont);
+        limbs_to_words(sp.b, b_mont);
     }
     FoldDigits* d_dg = (FoldDigits*)scratch_acquire(sizeof(FoldDigits), stream);
     if (!d_dg) return PLK_ERR_OOM;
@@ -509,14 +501,9 @@ int curve_fold_pairs_dev_impl(int curve, size_t m, const void* d_lo, const void*
     if (!d_scalars && (!a_mont || !b_mont)) return set_error(PLK_ERR_INVALID_ARG, "null scalar");
     if (m && (!d_lo || !d_hi || !d_out_xy || !d_out_zero)) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return fold_pairs_t<TweedledeeCurve>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
-        case PLK_CURVE_TWEEDLEDUM: return fold_pairs_t<TweedledumCurve>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
-        case PLK_CURVE_BLS12_377: return fold_pairs_t<Bls12377Curve>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
-        case PLK_CURVE_PALLAS: return fold_pairs_t<PallasCurve>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
-        case PLK_CURVE_VESTA: return fold_pairs_t<VestaCurve>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
+    return or_bad_curve(with_curve(curve, [&](auto t) {
+        return fold_pairs_t<tag_t<decltype(t)>>(m, d_lo, d_lo_zero, d_hi, d_hi_zero, a_mont, b_mont, d_out_xy, d_out_zero, stream, d_scalars, plus_lo);
+    }), curve);
 }
 
 }  // namespace plk

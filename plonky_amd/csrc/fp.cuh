@@ -543,6 +543,14 @@ template <class P> PLK_DI Fe<P> fe_half(const Fe<P>& a) {
     return r;
 }
 
+// an element from NL 32-bit words, e.g. of a kernel-argument struct the host filled with limbs_to_words (common.h)
+template <class P> PLK_DI Fe<P> fe_from_words(const uint32_t* w) {
+    Fe<P> r;
+#pragma unroll
+    for (int i = 0; i < P::NL; ++i) r.v[i] = w[i];
+    return r;
+}
+
 #ifdef __HIPCC__
 // ---- global / LDS movement: an element is NL/4 16-byte words (AoS, as the reference stores it) ----
 template <class P> PLK_DI Fe<P> fe_load(const uint4* p) {

@@ -263,21 +263,17 @@ namespace plk {
 
 static HaloScalar to_halo_scalar(const uint64_t* s) {
     HaloScalar h;
-    for (int k = 0; k < 4; ++k) {
-        h.v[2 * k] = (uint32_t)s[k];
-        h.v[2 * k + 1] = (uint32_t)(s[k] >> 32);
-    }
+    limbs_to_words(h.v, s);
     return h;
 }
 
-#define HALO_FIELD_SWITCH(field, CALL)                                        \
-    switch (field) {                                                          \
-        case PLK_FIELD_TWEEDLEDEE_BASE: { using P = TweedledeeBaseParams; CALL; } break;   \
-        case PLK_FIELD_TWEEDLEDUM_BASE: { using P = TweedledumBaseParams; CALL; } break;   \
-        case PLK_FIELD_BLS12_377_SCALAR: { using P = Bls12377ScalarParams; CALL; } break;  \
-        case PLK_FIELD_PALLAS_BASE: { using P = PallasBaseParams; CALL; } break;           \
-        default: { using P = VestaBaseParams; CALL; } break;                               \
-    }
+// launch(t) on the context's scalar field, t the tag of its parameter struct (a 4-limb field for every curve)
+template <class F> static int halo_with_sfield(const plk_halo_ctx* c, F&& launch) {
+    return or_bad_field(with_field4(c->sfield, [&](auto t) {
+        launch(t);
+        return PLK_OK;
+    }), c->sfield);
+}
 
 static size_t freeze_len(const plk_halo_ctx* c) { return (size_t)1 << (c->freeze_log > 40 ? 40 : c->freeze_log); }
 
@@ -287,7 +283,9 @@ static int halo_freeze(plk_halo_ctx* c) {
     PLK_TRY(msm_precompute_dev_impl(c->curve, c->m0 + 2, c->g, c->gz, 0, 0, c->stream, &c->mT, c->extra, 2));
     PLK_TRY(msm_reserve_workspaces_impl(c->mT, 2, c->stream));  // L_j and R_j are one batched call
     const unsigned blocks = (unsigned)((c->m0 + 255) / 256);
-    HALO_FIELD_SWITCH(c->sfield, (k_halo_fill<P><<<blocks, 256, 0, c->stream>>>((uint4*)c->coef, c->m0, (const uint4*)(c->dsc + 2 * 32))));
+    PLK_TRY(halo_with_sfield(c, [&](auto t) {
+        k_halo_fill<tag_t<decltype(t)>><<<blocks, 256, 0, c->stream>>>((uint4*)c->coef, c->m0, (const uint4*)(c->dsc + 2 * 32));
+    }));
     PLK_HIP_TRY(hipGetLastError());
     c->frozen = true;
     // (Replaying the ~20 launches of a frozen round's batched MSM from a hipGraph was measured: 39.6 against 39.2 ms for the whole
@@ -317,8 +315,11 @@ static int halo_next_stage(plk_halo_ctx* c) {
     c->virt_total = c->virt_left = d;
     c->m0 = c->n;
     // every generator of the stage's set starts with the coefficient c (the scale of the explicit set; 1 over the caller's tables)
-    HALO_FIELD_SWITCH(c->sfield, (k_halo_fill<P><<<(unsigned)((c->m0 + 255) / 256), 256, 0, c->stream>>>((uint4*)c->coef, c->m0, (const uint4*)(c->dsc + 2 * 32)),
-                                  k_halo_fill<P><<<1, 256, 0, c->stream>>>((uint4*)c->ratios, 1, nullptr)));
+    PLK_TRY(halo_with_sfield(c, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        k_halo_fill<P><<<(unsigned)((c->m0 + 255) / 256), 256, 0, c->stream>>>((uint4*)c->coef, c->m0, (const uint4*)(c->dsc + 2 * 32));
+        k_halo_fill<P><<<1, 256, 0, c->stream>>>((uint4*)c->ratios, 1, nullptr);
+    }));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -413,7 +414,7 @@ int halo_begin_dev_impl(int curve, size_t n, const void* d_a, const void* d_b, c
         memcpy(c->pin + 2 * pt, u_prime_scalar, 32);
         PLK_HIP_TRY(hipMemcpyAsync(c->dsc + 4 * 32, c->pin + 2 * pt, 32, hipMemcpyHostToDevice, stream));
     }
-    HALO_FIELD_SWITCH(c->sfield, (k_halo_fill<P><<<1, 256, 0, stream>>>((uint4*)(c->dsc + 2 * 32), 1, nullptr)));  // c = 1
+    PLK_TRY(halo_with_sfield(c, [&](auto t) { k_halo_fill<tag_t<decltype(t)>><<<1, 256, 0, stream>>>((uint4*)(c->dsc + 2 * 32), 1, nullptr); }));  // c = 1
     PLK_HIP_TRY(hipGetLastError());
     if (c->lead_ctx) {
         // generators of the caller's context beyond n never get a scalar
@@ -453,11 +454,14 @@ int halo_round_lr_impl(plk_halo_ctx* c, const uint64_t* l_blind, const uint64_t*
     if (blocks > HALO_PART_BLOCKS) blocks = HALO_PART_BLOCKS;
     const HaloScalar lb = to_halo_scalar(l_blind), rb = to_halo_scalar(r_blind);
     const bool beside = lead && !c->lead_inside;  // H and U' are not in the caller's tables: their scalars go to `hu`
-    HALO_FIELD_SWITCH(c->sfield, (k_halo_prepare<P><<<blocks, 256, 0, c->stream>>>((const uint4*)c->a, (const uint4*)c->b, m, m0, (const uint4*)c->coef,
-                                                                                     (const uint4*)(c->dsc + 2 * 32), (uint4*)sL, (uint4*)sR, (uint4*)c->part),
-                                  k_halo_close<P><<<1, 64, 0, c->stream>>>((const uint4*)c->part, blocks, lb, rb, !lead ? cnt : c->lead_inside ? c->lead_h : 0,
-                                                                           (uint4*)(beside ? c->hu : sL), (uint4*)(beside ? c->hu + 64 : sR), c->lead_u,
-                                                                           (const uint4*)(lead && c->lead_inside ? c->dsc + 4 * 32 : nullptr))));
+    PLK_TRY(halo_with_sfield(c, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        k_halo_prepare<P><<<blocks, 256, 0, c->stream>>>((const uint4*)c->a, (const uint4*)c->b, m, m0, (const uint4*)c->coef, (const uint4*)(c->dsc + 2 * 32),
+                                                         (uint4*)sL, (uint4*)sR, (uint4*)c->part);
+        k_halo_close<P><<<1, 64, 0, c->stream>>>((const uint4*)c->part, blocks, lb, rb, !lead ? cnt : c->lead_inside ? c->lead_h : 0,
+                                                 (uint4*)(beside ? c->hu : sL), (uint4*)(beside ? c->hu + 64 : sR), c->lead_u,
+                                                 (const uint4*)(lead && c->lead_inside ? c->dsc + 4 * 32 : nullptr));
+    }));
     PLK_HIP_TRY(hipGetLastError());
     // L_j and R_j leave the device as msm_execute's ProjectivePoints (halo.rs:93-101) and are normalised where the reference normalises
     // them, on the host: the inversion is the last ~35 us of the round's dependency chain on ONE GPU lane and ~2 us on a core
@@ -534,15 +538,18 @@ int halo_round_fold_impl(plk_halo_ctx* c, const uint64_t* u_j, const uint64_t* u
     } poison{c, false};
     const size_t m0 = (c->frozen || virt) ? c->m0 : 0;
     const size_t work = m > m0 ? m : m0;
-    HALO_FIELD_SWITCH(c->sfield, (k_halo_fold_scalars<P><<<(unsigned)((work + 255) / 256), 256, 0, c->stream>>>(
-                                     (uint4*)c->a, (uint4*)c->b, m, to_halo_scalar(u_j), to_halo_scalar(u_j_inv), (uint4*)c->coef, m0,
-                                     (uint4*)(c->frozen ? nullptr : c->dsc))));
+    PLK_TRY(halo_with_sfield(c, [&](auto t) {
+        k_halo_fold_scalars<tag_t<decltype(t)>><<<(unsigned)((work + 255) / 256), 256, 0, c->stream>>>(
+            (uint4*)c->a, (uint4*)c->b, m, to_halo_scalar(u_j), to_halo_scalar(u_j_inv), (uint4*)c->coef, m0, (uint4*)(c->frozen ? nullptr : c->dsc));
+    }));
     PLK_HIP_TRY(hipGetLastError());
     c->n = m;
     c->lr_done = false;
     poison.armed = true;
     if (virt) {
-        HALO_FIELD_SWITCH(c->sfield, (k_halo_lead_ratios<P><<<1, 64, 0, c->stream>>>((uint4*)c->ratios, (int)(c->virt_total - c->virt_left), (const uint4*)c->dsc)));
+        PLK_TRY(halo_with_sfield(c, [&](auto t) {
+            k_halo_lead_ratios<tag_t<decltype(t)>><<<1, 64, 0, c->stream>>>((uint4*)c->ratios, (int)(c->virt_total - c->virt_left), (const uint4*)c->dsc);
+        }));
         PLK_HIP_TRY(hipGetLastError());
         if (--c->virt_left == 0) {
             // the generators of the stage's rounds at once, scaled like the pairwise folds: G = [c] G~, c = c_0 prod u_k^-1 (dsc[2])

@@ -5,6 +5,7 @@
 // (tests/test_fp_host.py sweeps the same functions against Python integers).
 #include <cstring>
 
+#include "ec.cuh"
 #include "fp.cuh"
 
 namespace plk {
@@ -31,14 +32,11 @@ template <class P> static void to_affine_t(unsigned count, const uint8_t* xyz, c
 
 // curve: PLK_CURVE_* (include/plonky_hip.h).  Returns 0, or -1 for an unknown curve.
 int host_projective_to_affine(int curve, unsigned count, const uint8_t* xyz, const uint8_t* zero, uint8_t* xy) {
-    switch (curve) {
-        case 0: to_affine_t<TweedledeeBaseParams>(count, xyz, zero, xy); return 0;
-        case 1: to_affine_t<TweedledumBaseParams>(count, xyz, zero, xy); return 0;
-        case 2: to_affine_t<Bls12377BaseParams>(count, xyz, zero, xy); return 0;
-        case 3: to_affine_t<PallasBaseParams>(count, xyz, zero, xy); return 0;
-        case 4: to_affine_t<VestaBaseParams>(count, xyz, zero, xy); return 0;
-    }
-    return -1;
+    const int rc = with_curve(curve, [&](auto t) {
+        to_affine_t<typename tag_t<decltype(t)>::FP>(count, xyz, zero, xy);
+        return 0;
+    });
+    return rc == PLK_NO_MATCH ? -1 : rc;
 }
 
 }  // namespace plk

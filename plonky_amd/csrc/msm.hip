@@ -503,7 +503,6 @@ struct plk_msm_ctx {
 
 namespace plk {
 
-static int scalar_bits(int curve) { return curve == PLK_CURVE_BLS12_377 ? 253 : 255; }
 static int ilog2_ceil(uint64_t v) {
     int b = 0;
     while (((uint64_t)1 << b) < v) ++b;
@@ -513,7 +512,7 @@ static int ilog2_ceil(uint64_t v) {
 static int choose_window(size_t n, int curve) {
     int lg = 0;
     while (((size_t)1 << (lg + 1)) <= n) ++lg;
-    const int bits = scalar_bits(curve) + 1;
+    const int bits = curve_scalar_bits(curve) + 1;
     auto digits = [&](int c) { return (bits + c - 1) / c; };
     auto top_bits = [&](int c) { return bits - (digits(c) - 1) * c; };
     int c;
@@ -825,9 +824,9 @@ static int msm_configure(plk_msm_ctx* ctx, int curve, size_t n, unsigned window_
     // table-free mode on the prime-order curves: split every scalar along the endomorphism (glv.cuh) - 2n points, half the windows
     const bool glv = table_free && n > 0 && curve != PLK_CURVE_BLS12_377 && !getenv("PLK_MSM_NO_GLV");
     const size_t n_eff = glv ? 2 * n : n;
-    int c = window_bits ? (int)window_bits : (table_free ? choose_window_table_free(n_eff ? n_eff : 1, (glv ? GLV_BITS : scalar_bits(curve)) + 1) : choose_window(n ? n : 1, curve));
+    int c = window_bits ? (int)window_bits : (table_free ? choose_window_table_free(n_eff ? n_eff : 1, (glv ? GLV_BITS : curve_scalar_bits(curve)) + 1) : choose_window(n ? n : 1, curve));
     if (c < 2 || c > MSM_MAX_WINDOW) return set_error(PLK_ERR_INVALID_ARG, "window_bits %d outside [2, %d]", c, MSM_MAX_WINDOW);
-    const int windows = ((glv ? GLV_BITS : scalar_bits(curve)) + 1 + c - 1) / c;
+    const int windows = ((glv ? GLV_BITS : curve_scalar_bits(curve)) + 1 + c - 1) / c;
     if (table_free && c > MSM_TF_MAX_WINDOW)
         return set_error(PLK_ERR_INVALID_ARG, "table-free mode: window_bits %d above %d", c, MSM_TF_MAX_WINDOW);
     if (table_free) {
@@ -935,13 +934,9 @@ int msm_precompute_dev_impl(int curve, size_t n, const void* d_bases, const void
     ctx->device = dev;
     ctx->auto_window = window_bits == 0 && also_count == 0;
     int rc = msm_configure(ctx, curve, n, window_bits, (flags & PLK_MSM_TABLE_FREE) != 0);
-    if (rc == PLK_OK) switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: rc = msm_precompute_t<TweedledeeCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); break;
-        case PLK_CURVE_TWEEDLEDUM: rc = msm_precompute_t<TweedledumCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); break;
-        case PLK_CURVE_PALLAS: rc = msm_precompute_t<PallasCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); break;
-        case PLK_CURVE_VESTA: rc = msm_precompute_t<VestaCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); break;
-        default: rc = msm_precompute_t<Bls12377Curve>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); break;
-    }
+    if (rc == PLK_OK)
+        rc = or_bad_curve(with_curve(curve, [&](auto t) { return msm_precompute_t<tag_t<decltype(t)>>(ctx, d_bases, d_zero, d_extra, n_extra, stream, also_n, also_count); }),
+                          curve);
     if (rc != PLK_OK) {
         delete ctx;
         return rc;
@@ -958,13 +953,7 @@ int msm_rebind_dev_impl(plk_msm_ctx* ctx, size_t n, const void* d_bases, const v
     std::lock_guard<std::mutex> lk(ctx->mu);
     const int curve = ctx->curve;
     PLK_TRY(msm_configure(ctx, curve, n, 0, true));
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return msm_rebind_t<TweedledeeCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream);
-        case PLK_CURVE_TWEEDLEDUM: return msm_rebind_t<TweedledumCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream);
-        case PLK_CURVE_PALLAS: return msm_rebind_t<PallasCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream);
-        case PLK_CURVE_VESTA: return msm_rebind_t<VestaCurve>(ctx, d_bases, d_zero, d_extra, n_extra, stream);
-        default: return msm_rebind_t<Bls12377Curve>(ctx, d_bases, d_zero, d_extra, n_extra, stream);
-    }
+    return or_bad_curve(with_curve(curve, [&](auto t) { return msm_rebind_t<tag_t<decltype(t)>>(ctx, d_bases, d_zero, d_extra, n_extra, stream); }), curve);
 }
 
 static uint32_t* head_bucket_of(const plk_msm_ctx* ctx, const MsmWork& w) {
@@ -1175,13 +1164,8 @@ int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars
         const uint32_t bp = (parts && parts->bucket_parts) ? parts->bucket_part[b] : 0u, bps = (parts && parts->bucket_parts) ? parts->bucket_parts[b] : 1u;
         uint8_t* oxy = (uint8_t*)d_out_xy + (size_t)b * out_stride;
         uint8_t* oz = (uint8_t*)d_out_zero + b;
-        switch (ctx->curve) {
-            case PLK_CURVE_TWEEDLEDEE: return msm_execute_t<TweedledeeCurve>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps);
-            case PLK_CURVE_TWEEDLEDUM: return msm_execute_t<TweedledumCurve>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps);
-            case PLK_CURVE_PALLAS: return msm_execute_t<PallasCurve>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps);
-            case PLK_CURVE_VESTA: return msm_execute_t<VestaCurve>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps);
-            default: return msm_execute_t<Bls12377Curve>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps);
-        }
+        return or_bad_curve(with_curve(ctx->curve, [&](auto t) { return msm_execute_t<tag_t<decltype(t)>>(ctx, w, sc, oxy, oz, st, phases, first, count, bp, bps); }),
+                            ctx->curve);
     };
     static const bool no_batching = getenv("PLK_MSM_NO_OVERLAP") != nullptr;  // every MSM of a batch start to end, one by one
     if (batch == 1 || ctx->profiling || no_batching) {
@@ -1198,14 +1182,7 @@ int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars
     while (group > 2 && ctx->ws_bytes * group > budget) --group;
     while (ctx->ws.size() < group) {
         ctx->ws.emplace_back();
-        int rc;
-        switch (ctx->curve) {
-            case PLK_CURVE_TWEEDLEDEE: rc = msm_alloc_work<TweedledeeCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_TWEEDLEDUM: rc = msm_alloc_work<TweedledumCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_PALLAS: rc = msm_alloc_work<PallasCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_VESTA: rc = msm_alloc_work<VestaCurve>(ctx, ctx->ws.back(), stream); break;
-            default: rc = msm_alloc_work<Bls12377Curve>(ctx, ctx->ws.back(), stream); break;
-        }
+        const int rc = or_bad_curve(with_curve(ctx->curve, [&](auto t) { return msm_alloc_work<tag_t<decltype(t)>>(ctx, ctx->ws.back(), stream); }), ctx->curve);
         if (rc != PLK_OK) {
             ctx->ws.back().release();
             ctx->ws.pop_back();
@@ -1216,13 +1193,7 @@ int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars
     }
     auto reduce = [&](const TailBatch& tb, hipStream_t st) -> int {
         auto nomark = [] {};
-        switch (ctx->curve) {
-            case PLK_CURVE_TWEEDLEDEE: return msm_reduce_t<TweedledeeCurve>(ctx, tb, st, nomark);
-            case PLK_CURVE_TWEEDLEDUM: return msm_reduce_t<TweedledumCurve>(ctx, tb, st, nomark);
-            case PLK_CURVE_PALLAS: return msm_reduce_t<PallasCurve>(ctx, tb, st, nomark);
-            case PLK_CURVE_VESTA: return msm_reduce_t<VestaCurve>(ctx, tb, st, nomark);
-            default: return msm_reduce_t<Bls12377Curve>(ctx, tb, st, nomark);
-        }
+        return or_bad_curve(with_curve(ctx->curve, [&](auto t) { return msm_reduce_t<tag_t<decltype(t)>>(ctx, tb, st, nomark); }), ctx->curve);
     };
     // Pipelined reductions: the reduction of a vector is mostly latency (chains on few points) plus
     // 0.1 ms of full-width row / column sums; on a second stream it runs under the ordering and accumulation of the NEXT vector
@@ -1299,16 +1270,7 @@ int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars
             }
             tb.s[k] = tail_slot(ctx, ctx->ws[k], (uint8_t*)d_out_xy + (size_t)b * out_stride, (uint8_t*)d_out_zero + b);
         }
-        int rc;
-        auto nomark = [] {};
-        switch (ctx->curve) {
-            case PLK_CURVE_TWEEDLEDEE: rc = msm_reduce_t<TweedledeeCurve>(ctx, tb, stream, nomark); break;
-            case PLK_CURVE_TWEEDLEDUM: rc = msm_reduce_t<TweedledumCurve>(ctx, tb, stream, nomark); break;
-            case PLK_CURVE_PALLAS: rc = msm_reduce_t<PallasCurve>(ctx, tb, stream, nomark); break;
-            case PLK_CURVE_VESTA: rc = msm_reduce_t<VestaCurve>(ctx, tb, stream, nomark); break;
-            default: rc = msm_reduce_t<Bls12377Curve>(ctx, tb, stream, nomark); break;
-        }
-        PLK_TRY(rc);
+        PLK_TRY(reduce(tb, stream));
         for (unsigned k = 0; k < cnt; ++k) work_done(ctx->ws[k], stream);
     }
     return PLK_OK;
@@ -1327,14 +1289,11 @@ template <class FP> __global__ void k_affine_to_projective(const uint4* __restri
 int msm_affine_to_projective_impl(int curve, unsigned batch, const void* d_xy, const void* d_zero, void* d_xyz, hipStream_t stream) {
     if (batch == 0) return PLK_OK;
     const unsigned blocks = (batch + 63) / 64;
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: k_affine_to_projective<TweedledeeBaseParams><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch); break;
-        case PLK_CURVE_TWEEDLEDUM: k_affine_to_projective<TweedledumBaseParams><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch); break;
-        case PLK_CURVE_PALLAS: k_affine_to_projective<PallasBaseParams><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch); break;
-        case PLK_CURVE_VESTA: k_affine_to_projective<VestaBaseParams><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch); break;
-        case PLK_CURVE_BLS12_377: k_affine_to_projective<Bls12377BaseParams><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch); break;
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using FP = typename tag_t<decltype(t)>::FP;
+        k_affine_to_projective<FP><<<blocks, 64, 0, stream>>>((const uint4*)d_xy, (const uint8_t*)d_zero, (uint4*)d_xyz, batch);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -1384,7 +1343,7 @@ std::vector<plk_msm_ctx*>& msm_ctx_peers(plk_msm_ctx* ctx) { return ctx->peers; 
 std::vector<plk_msm_ctx*>& msm_ctx_shards(plk_msm_ctx* ctx) { return ctx->shards; }
 
 // msm_precompute with the reference's output (curve_msm.rs:27-52): powers_per_generator[i][j] = [2^(w j)] G_i, j < ceil(BITS / w)
-int msm_table_digits(int curve, unsigned w) { return w ? (scalar_bits(curve) + (int)w - 1) / (int)w : -1; }
+int msm_table_digits(int curve, unsigned w) { return w ? (curve_scalar_bits(curve) + (int)w - 1) / (int)w : -1; }
 
 template <class C>
 static int msm_reference_table_t(size_t n, const void* d_bases, const void* d_zero, int w, int digits, void* d_out_xy, void* d_out_zero,
@@ -1410,30 +1369,16 @@ int msm_reference_table_dev_impl(int curve, size_t n, const void* d_bases, const
     if (!d_bases || !d_out_xy || !d_out_zero) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
     const int digits = msm_table_digits(curve, w);
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return msm_reference_table_t<TweedledeeCurve>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_TWEEDLEDUM: return msm_reference_table_t<TweedledumCurve>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_PALLAS: return msm_reference_table_t<PallasCurve>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream);
-        case PLK_CURVE_VESTA: return msm_reference_table_t<VestaCurve>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream);
-        default: return msm_reference_table_t<Bls12377Curve>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream);
-    }
+    return or_bad_curve(with_curve(curve, [&](auto t) { return msm_reference_table_t<tag_t<decltype(t)>>(n, d_bases, d_zero, (int)w, digits, d_out_xy, d_out_zero, stream); }),
+                        curve);
 }
 
 int curve_sum_affine_dev_impl(int curve, size_t k, const void* d_pts, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream) {
-    switch (curve) {
-#define CASE(ID, C)                                                                                                                     \
-    case ID:                                                                                                                            \
-        k_sum_affine<C><<<1, 64, 64 * 4 * C::FP::NL * 4, stream>>>((const uint4*)d_pts, (const uint8_t*)d_zero, k, (uint4*)d_out_xy,     \
-                                                                    (uint8_t*)d_out_zero);                                              \
-        break;
-        CASE(PLK_CURVE_TWEEDLEDEE, TweedledeeCurve)
-        CASE(PLK_CURVE_TWEEDLEDUM, TweedledumCurve)
-        CASE(PLK_CURVE_BLS12_377, Bls12377Curve)
-        CASE(PLK_CURVE_PALLAS, PallasCurve)
-        CASE(PLK_CURVE_VESTA, VestaCurve)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using C = tag_t<decltype(t)>;
+        k_sum_affine<C><<<1, 64, 64 * 4 * C::FP::NL * 4, stream>>>((const uint4*)d_pts, (const uint8_t*)d_zero, k, (uint4*)d_out_xy, (uint8_t*)d_out_zero);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -1452,19 +1397,12 @@ int msm_combine_partials_dev_impl(int curve, unsigned world, unsigned batch, uns
     PLK_TRY(ensure_device());
     const unsigned slots = whole_per_rank + (batch - whole_per_rank * world);
     const size_t rec = msm_partials_bytes(curve, slots);
-    switch (curve) {
-#define CASE(ID, C)                                                                                                                                     \
-    case ID:                                                                                                                                            \
-        k_combine_partials<C><<<batch, 64, 64 * 4 * C::FP::NL * 4, stream>>>((const uint8_t*)d_gathered, rec, world, slots, whole_per_rank,            \
-                                                                             (uint4*)d_out_xy, (uint8_t*)d_out_zero);                                   \
-        break;
-        CASE(PLK_CURVE_TWEEDLEDEE, TweedledeeCurve)
-        CASE(PLK_CURVE_TWEEDLEDUM, TweedledumCurve)
-        CASE(PLK_CURVE_BLS12_377, Bls12377Curve)
-        CASE(PLK_CURVE_PALLAS, PallasCurve)
-        CASE(PLK_CURVE_VESTA, VestaCurve)
-#undef CASE
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using C = tag_t<decltype(t)>;
+        k_combine_partials<C><<<batch, 64, 64 * 4 * C::FP::NL * 4, stream>>>((const uint8_t*)d_gathered, rec, world, slots, whole_per_rank, (uint4*)d_out_xy,
+                                                                             (uint8_t*)d_out_zero);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -1478,18 +1416,12 @@ int msm_debug_digits_impl(int curve, unsigned window_bits, size_t n, const void*
     PLK_TRY(ensure_device());
     OrdCfg o{};
     o.c = (int)window_bits;
-    o.windows = (scalar_bits(curve) + 1 + o.c - 1) / o.c;
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: return msm_launch_digits<TweedledeeCurve>(d_scalars, n, o, d_digits, stream);
-        case PLK_CURVE_TWEEDLEDUM: return msm_launch_digits<TweedledumCurve>(d_scalars, n, o, d_digits, stream);
-        case PLK_CURVE_PALLAS: return msm_launch_digits<PallasCurve>(d_scalars, n, o, d_digits, stream);
-        case PLK_CURVE_VESTA: return msm_launch_digits<VestaCurve>(d_scalars, n, o, d_digits, stream);
-        default: return msm_launch_digits<Bls12377Curve>(d_scalars, n, o, d_digits, stream);
-    }
+    o.windows = (curve_scalar_bits(curve) + 1 + o.c - 1) / o.c;
+    return or_bad_curve(with_curve(curve, [&](auto t) { return msm_launch_digits<tag_t<decltype(t)>>(d_scalars, n, o, d_digits, stream); }), curve);
 }
 int msm_debug_digit_count(int curve, unsigned window_bits) {
     if (curve < 0 || curve > PLK_CURVE_VESTA || window_bits < 2 || window_bits > (unsigned)MSM_MAX_WINDOW) return -1;
-    return (scalar_bits(curve) + 1 + (int)window_bits - 1) / (int)window_bits;
+    return (curve_scalar_bits(curve) + 1 + (int)window_bits - 1) / (int)window_bits;
 }
 
 // workspaces for batches of up to `count` vectors, allocated ahead of the first batched execution
@@ -1501,14 +1433,7 @@ int msm_reserve_workspaces_impl(plk_msm_ctx* ctx, unsigned count, hipStream_t st
     if (count > (unsigned)TAIL_MAX) count = TAIL_MAX;
     while (ctx->ws.size() < count) {
         ctx->ws.emplace_back();
-        int rc;
-        switch (ctx->curve) {
-            case PLK_CURVE_TWEEDLEDEE: rc = msm_alloc_work<TweedledeeCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_TWEEDLEDUM: rc = msm_alloc_work<TweedledumCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_PALLAS: rc = msm_alloc_work<PallasCurve>(ctx, ctx->ws.back(), stream); break;
-            case PLK_CURVE_VESTA: rc = msm_alloc_work<VestaCurve>(ctx, ctx->ws.back(), stream); break;
-            default: rc = msm_alloc_work<Bls12377Curve>(ctx, ctx->ws.back(), stream); break;
-        }
+        const int rc = or_bad_curve(with_curve(ctx->curve, [&](auto t) { return msm_alloc_work<tag_t<decltype(t)>>(ctx, ctx->ws.back(), stream); }), ctx->curve);
         if (rc != PLK_OK) {
             ctx->ws.back().release();
             ctx->ws.pop_back();
@@ -1526,13 +1451,13 @@ int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t qu
     if (!d_cnt) return PLK_ERR_OOM;
     (void)hipMemsetAsync(d_cnt, 0, 32, nullptr);
     const unsigned blocks = (quads * 4 + 255) / 256;
-    switch (curve) {
-        case PLK_CURVE_TWEEDLEDEE: k_selftest_quad<TweedledeeCurve><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt); break;
-        case PLK_CURVE_TWEEDLEDUM: k_selftest_quad<TweedledumCurve><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt); break;
-        case PLK_CURVE_BLS12_377: k_selftest_quad<Bls12377Curve><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt); break;
-        case PLK_CURVE_PALLAS: k_selftest_quad<PallasCurve><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt); break;
-        case PLK_CURVE_VESTA: k_selftest_quad<VestaCurve><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt); break;
-        default: scratch_release(d_cnt, nullptr); return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
+    const int rc = with_curve(curve, [&](auto t) {
+        k_selftest_quad<tag_t<decltype(t)>><<<blocks, 256>>>((const uint4*)d_pts, n, d_cnt);
+        return PLK_OK;
+    });
+    if (rc != PLK_OK) {
+        scratch_release(d_cnt, nullptr);
+        return or_bad_curve(rc, curve);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(counts, d_cnt, 32, hipMemcpyDeviceToHost);
@@ -1543,17 +1468,10 @@ int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t qu
 
 int curve_gen_bases_dev_impl(int curve, size_t n, uint64_t first, const void* d_g0d, void* d_out, hipStream_t stream) {
     if (n == 0) return PLK_OK;
-    switch (curve) {
-#define CASE(ID, C)                                                                                                          \
-    case ID: k_gen_bases<C><<<(unsigned)((n + 127) / 128), 128, 0, stream>>>((const uint4*)d_g0d, (uint4*)d_out, n, first); break;
-        CASE(PLK_CURVE_TWEEDLEDEE, TweedledeeCurve)
-        CASE(PLK_CURVE_TWEEDLEDUM, TweedledumCurve)
-        CASE(PLK_CURVE_BLS12_377, Bls12377Curve)
-        CASE(PLK_CURVE_PALLAS, PallasCurve)
-        CASE(PLK_CURVE_VESTA, VestaCurve)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        k_gen_bases<tag_t<decltype(t)>><<<(unsigned)((n + 127) / 128), 128, 0, stream>>>((const uint4*)d_g0d, (uint4*)d_out, n, first);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }

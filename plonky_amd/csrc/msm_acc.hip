@@ -307,11 +307,7 @@ void msm_launch_accumulate(unsigned blocks, hipStream_t stream, const void* tab,
     template int msm_accumulate_blocks_per_cu<C>();                                                                                    \
     template void msm_launch_accumulate<C>(unsigned, hipStream_t, const void*, const void*, const void*, void*, void*, void*, void*, void*, uint32_t*, uint32_t, \
                                            const uint32_t*, int, uint32_t, uint32_t);
-PLK_ACC_INSTANTIATE(TweedledeeCurve)
-PLK_ACC_INSTANTIATE(TweedledumCurve)
-PLK_ACC_INSTANTIATE(Bls12377Curve)
-PLK_ACC_INSTANTIATE(PallasCurve)
-PLK_ACC_INSTANTIATE(VestaCurve)
+PLK_FOR_EACH_CURVE(PLK_ACC_INSTANTIATE)
 #undef PLK_ACC_INSTANTIATE
 
 // ---- the checked build (-DPLK_CHECKED: msm_acc_checked.o + msm_order_checked.o; include/plonky_hip.h) ----

@@ -979,11 +979,7 @@ template <class C> int msm_launch_digits(const void* d_scalars, size_t n, const 
     template int msm_launch_glv_split<C>(const void*, size_t, void*, hipStream_t);                \
     template int msm_launch_order_stage<C>(int, const OrdCfg&, const OrdBuffers&, hipStream_t);   \
     template int msm_launch_digits<C>(const void*, size_t, const OrdCfg&, void*, hipStream_t);
-PLK_ORD_INSTANTIATE(TweedledeeCurve)
-PLK_ORD_INSTANTIATE(TweedledumCurve)
-PLK_ORD_INSTANTIATE(Bls12377Curve)
-PLK_ORD_INSTANTIATE(PallasCurve)
-PLK_ORD_INSTANTIATE(VestaCurve)
+PLK_FOR_EACH_CURVE(PLK_ORD_INSTANTIATE)
 #undef PLK_ORD_INSTANTIATE
 
 PLK_CHK_READER(msm_order_checked_failures)

@@ -631,10 +631,8 @@ template <class C> int msm_launch_reduce_stage(int stage, const TailGeom& g, con
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
-template int msm_launch_reduce_stage<TweedledeeCurve>(int, const TailGeom&, const TailBatch&, hipStream_t);
-template int msm_launch_reduce_stage<TweedledumCurve>(int, const TailGeom&, const TailBatch&, hipStream_t);
-template int msm_launch_reduce_stage<Bls12377Curve>(int, const TailGeom&, const TailBatch&, hipStream_t);
-template int msm_launch_reduce_stage<PallasCurve>(int, const TailGeom&, const TailBatch&, hipStream_t);
-template int msm_launch_reduce_stage<VestaCurve>(int, const TailGeom&, const TailBatch&, hipStream_t);
+#define PLK_TAIL_INSTANTIATE(C) template int msm_launch_reduce_stage<C>(int, const TailGeom&, const TailBatch&, hipStream_t);
+PLK_FOR_EACH_CURVE(PLK_TAIL_INSTANTIATE)
+#undef PLK_TAIL_INSTANTIATE
 
 }  // namespace plk

@@ -723,17 +723,7 @@ static int get_plan(int field, unsigned log_n, std::shared_ptr<NttPlan>& out) {
     pl->log_n = (int)log_n;
     pl->device = dev;
     pl->pass_log = plan_passes((int)log_n);
-    int rc;
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: rc = build_plan_t<TweedledeeBaseParams>(*pl); break;
-        case PLK_FIELD_TWEEDLEDUM_BASE: rc = build_plan_t<TweedledumBaseParams>(*pl); break;
-        case PLK_FIELD_BLS12_377_SCALAR: rc = build_plan_t<Bls12377ScalarParams>(*pl); break;
-        case PLK_FIELD_BLS12_377_BASE: rc = build_plan_t<Bls12377BaseParams>(*pl); break;
-        case PLK_FIELD_PALLAS_BASE: rc = build_plan_t<PallasBaseParams>(*pl); break;
-        case PLK_FIELD_VESTA_BASE: rc = build_plan_t<VestaBaseParams>(*pl); break;
-        default: return set_error(PLK_ERR_INVALID_ARG, "field %d has no NTT entry point", field);
-    }
-    if (rc != PLK_OK) return rc;
+    PLK_TRY(or_invalid(with_field(field, [&](auto t) { return build_plan_t<tag_t<decltype(t)>>(*pl); }), "field %d has no NTT entry point", field));
     g_plans[key] = pl;
     out = pl;
     return PLK_OK;
@@ -866,19 +856,14 @@ static int ntt_dispatch(int field, unsigned log_n, int inverse, unsigned batch, 
     if (log_n > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_n %u too large (max 30)", log_n);
     std::shared_ptr<NttPlan> pl;
     PLK_TRY(get_plan(field, log_n, pl));
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return run_plan_t<TweedledeeBaseParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return run_plan_t<TweedledumBaseParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return run_plan_t<Bls12377ScalarParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-        case PLK_FIELD_BLS12_377_BASE:
-            // only the plain transform and its zero-padded form (fft_with_precomputation, fft.rs:61-80); the polynomial callers' hooks
-            // (coset factors, denominators) belong to the circuit's scalar fields
-            if (hooks && (hooks->in_lo || hooks->out_tab || hooks->out_lo)) return set_error(PLK_ERR_INVALID_ARG, "field %d has no polynomial entry points", field);
-            return run_plan_t<Bls12377BaseParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-        case PLK_FIELD_PALLAS_BASE: return run_plan_t<PallasBaseParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-        case PLK_FIELD_VESTA_BASE: return run_plan_t<VestaBaseParams>(*pl, inverse, batch, d_in, d_out, hooks, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d has no NTT entry point", field);
+    return or_invalid(with_field(field, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        // the 6-limb field: only the plain transform and its zero-padded form (fft_with_precomputation, fft.rs:61-80); the polynomial
+        // callers' hooks (coset factors, denominators) belong to the circuit's scalar fields
+        if (P::FIELD_ID == PLK_FIELD_BLS12_377_BASE && hooks && (hooks->in_lo || hooks->out_tab || hooks->out_lo))
+            return set_error(PLK_ERR_INVALID_ARG, "field %d has no polynomial entry points", field);
+        return run_plan_t<P>(*pl, inverse, batch, d_in, d_out, hooks, stream);
+    }), "field %d has no NTT entry point", field);
 }
 
 int ntt_dev_impl(int field, unsigned log_n, int inverse, unsigned batch, const void* d_in, void* d_out, hipStream_t stream) {
@@ -899,16 +884,10 @@ int ntt_reference_table_dev_impl(int field, unsigned log_n, void* d_out, hipStre
     const int log_t = (int)log_n > INNER_LOG ? (int)log_n : INNER_LOG;
     const size_t total = ((size_t)2 << log_n) - 1;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    switch (field) {
-#define CASE(ID, P) case ID: k_ntt_reference_table<P><<<blocks, 256, 0, stream>>>((uint4*)d_out, (const uint4*)pl->pw, log_t, (int)log_n); break;
-        CASE(PLK_FIELD_TWEEDLEDEE_BASE, TweedledeeBaseParams)
-        CASE(PLK_FIELD_TWEEDLEDUM_BASE, TweedledumBaseParams)
-        CASE(PLK_FIELD_BLS12_377_SCALAR, Bls12377ScalarParams)
-        CASE(PLK_FIELD_BLS12_377_BASE, Bls12377BaseParams)
-        CASE(PLK_FIELD_PALLAS_BASE, PallasBaseParams)
-        CASE(PLK_FIELD_VESTA_BASE, VestaBaseParams)
-#undef CASE
-    }
+    PLK_TRY(or_bad_field(with_field(field, [&](auto t) {
+        k_ntt_reference_table<tag_t<decltype(t)>><<<blocks, 256, 0, stream>>>((uint4*)d_out, (const uint4*)pl->pw, log_t, (int)log_n);
+        return PLK_OK;
+    }), field));
     PLK_HIP_TRY(hipGetLastError());
     // the plan (and its power table) must outlive the kernel: the cache may be cleared by another thread
     PLK_HIP_TRY(hipStreamSynchronize(stream));

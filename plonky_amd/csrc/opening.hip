@@ -60,27 +60,20 @@ struct OpenUs {
     uint32_t u[OPEN_MAX_US][8];
 };
 
-template <class P> PLK_DI Fe<P> fe_from_words8(const uint32_t* w) {
-    Fe<P> r;
-#pragma unroll
-    for (int i = 0; i < P::NL; ++i) r.v[i] = w[i];
-    return r;
-}
-
 template <class P> __global__ void __launch_bounds__(64) k_open_describe(OpenChunk c, unsigned first, unsigned count, int with_scalars, OpenDesc d) {
     const unsigned i = threadIdx.x;
     if (i >= count) return;
     d.ptr[first + i] = (const uint4*)c.ptr[i];
     d.len[first + i] = c.len[i];
     d.tile_off[first + i] = c.tile_off[i];
-    if (with_scalars) limbs_store<P>(d.scalar, first + i, fz_from_fe<P>(to_rprime<P>(fe_from_words8<P>(c.scalar[i]))));
+    if (with_scalars) limbs_store<P>(d.scalar, first + i, fz_from_fe<P>(to_rprime<P>(fe_from_words<P>(c.scalar[i]))));
 }
 
 // per point k: ytab[k][m] = x^(256 m), m < 24 (limb form), ltab[k][l] = x^l, l < 256 (words) - both R'-form - and xtile[k] = x^OPEN_TILE (R-form)
 template <class P>
 __global__ void __launch_bounds__(OPEN_LANES) k_open_tables(OpenPoints pts, uint32_t* __restrict__ ytab, uint4* __restrict__ ltab, uint4* __restrict__ xtile) {
     const int k = blockIdx.x, l = threadIdx.x;
-    const Fe<P> x = fe_from_words8<P>(pts.x[k]);
+    const Fe<P> x = fe_from_words<P>(pts.x[k]);
     fe_store<P>(ltab + ((size_t)k * OPEN_LANES + l) * (P::NL / 4), to_rprime<P>(fe_pow_u64<P>(x, (uint64_t)l)));
     if (l < OPEN_PER_LANE) limbs_store<P>(ytab, (size_t)k * OPEN_PER_LANE + l, fz_from_fe<P>(to_rprime<P>(fe_pow_u64<P>(x, (uint64_t)OPEN_LANES * l))));
     if (l == OPEN_PER_LANE) fe_store<P>(xtile + k * (P::NL / 4), fe_pow_u64<P>(x, (uint64_t)OPEN_TILE));
@@ -221,20 +214,20 @@ __global__ void __launch_bounds__(OPEN_LANES) k_open_pow_tables(OpenPoints pts, 
     if (i >= per * (size_t)np) return;
     const int k = (int)(i / per);
     const size_t e = i % per;
-    const Fe<P> x = fe_from_words8<P>(pts.x[k]);
+    const Fe<P> x = fe_from_words<P>(pts.x[k]);
     if (e < OPEN_LO) {
         fe_store<P>(lo + ((size_t)k * OPEN_LO + e) * W, fe_pow_u64<P>(x, e));
     } else {
         Fe<P> y = x;
         for (int s = 0; s < OPEN_LO_LOG; ++s) y = fe_sqr<P>(y);
-        const Fe<P> vk = fe_pow_u64<P>(fe_from_words8<P>(pts.v), (uint64_t)k);
+        const Fe<P> vk = fe_pow_u64<P>(fe_from_words<P>(pts.v), (uint64_t)k);
         fe_store<P>(hi + ((size_t)k * nhi + (e - OPEN_LO)) * W, to_rprime<P>(fe_mul<P>(vk, fe_pow_u64<P>(y, e - OPEN_LO))));
     }
 }
 // halo_s (plonk_util.rs:311-326): element i = prod_j (bit j of i ? u : 1 / u)[k - 1 - j].  The k inversions are one lane each of a launch
 // of their own (uinv); lo[a]: the factors of bits 0..9, hi[b]: the others
 template <class P> __global__ void __launch_bounds__(64) k_halo_s_inverses(OpenUs us, unsigned k, uint4* __restrict__ uinv) {
-    if (threadIdx.x < k) fe_store<P>(uinv + threadIdx.x * (P::NL / 4), fe_inv_safegcd<P>(fe_from_words8<P>(us.u[threadIdx.x])));
+    if (threadIdx.x < k) fe_store<P>(uinv + threadIdx.x * (P::NL / 4), fe_inv_safegcd<P>(fe_from_words<P>(us.u[threadIdx.x])));
 }
 template <class P>
 __global__ void __launch_bounds__(OPEN_LANES) k_halo_s_tables(OpenUs us, const uint4* __restrict__ uinv, unsigned k, size_t nlo, size_t nhi, uint4* __restrict__ lo,
@@ -248,7 +241,7 @@ __global__ void __launch_bounds__(OPEN_LANES) k_halo_s_tables(OpenUs us, const u
     Fe<P> r = fe_one<P>();
     for (unsigned j = j0; j < j1; ++j) {
         const unsigned idx = k - 1 - j;
-        r = fe_mul<P>(r, ((bits >> (j - j0)) & 1) ? fe_from_words8<P>(us.u[idx]) : fe_load<P>(uinv + idx * W));
+        r = fe_mul<P>(r, ((bits >> (j - j0)) & 1) ? fe_from_words<P>(us.u[idx]) : fe_load<P>(uinv + idx * W));
     }
     if (low) fe_store<P>(lo + i * W, r);
     else fe_store<P>(hi + (i - nlo) * W, to_rprime<P>(r));
@@ -273,13 +266,6 @@ __global__ void __launch_bounds__(OPEN_LANES) k_open_two_level(const uint4* __re
 }
 
 // ---- host side ----
-static void put_words8(uint32_t* dst, const uint64_t* src) {
-    for (int k = 0; k < 4; ++k) {
-        dst[2 * k] = (uint32_t)src[k];
-        dst[2 * k + 1] = (uint32_t)(src[k] >> 32);
-    }
-}
-
 static int check_polys(unsigned n_polys, const void* const* d_polys, const size_t* lens) {
     if (n_polys && (!d_polys || !lens)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     for (unsigned i = 0; i < n_polys; ++i)
@@ -305,7 +291,7 @@ static int describe(ScratchSet& ss, unsigned n_polys, const void* const* d_polys
             c.len[i] = lens[first + i];
             c.tile_off[i] = tiles;
             tiles += (lens[first + i] + OPEN_TILE - 1) / OPEN_TILE;
-            if (scalars) put_words8(c.scalar[i], scalars + (size_t)(first + i) * 4);
+            if (scalars) limbs_to_words(c.scalar[i], scalars + (size_t)(first + i) * 4);
         }
         k_open_describe<P><<<1, 64, 0, ss.stream>>>(c, first, count, scalars ? 1 : 0, d);
     }
@@ -326,7 +312,7 @@ static int eval_polys_t(unsigned n_polys, const void* const* d_polys, const size
     uint4* part = (uint4*)ss.get(tiles * n_points * 32);
     if (!ytab || !ltab || !xtile || !part) return PLK_ERR_OOM;
     OpenPoints pts = {};
-    for (unsigned k = 0; k < n_points; ++k) put_words8(pts.x[k], points + (size_t)k * 4);
+    for (unsigned k = 0; k < n_points; ++k) limbs_to_words(pts.x[k], points + (size_t)k * 4);
     k_open_tables<P><<<n_points, OPEN_LANES, 0, stream>>>(pts, ytab, ltab, xtile);
     const size_t max_tiles = (max_len + OPEN_TILE - 1) / OPEN_TILE;
     for (unsigned poly0 = 0; poly0 < n_polys && max_tiles; poly0 += 32768u) {
@@ -359,8 +345,8 @@ template <class P> static int build_b_t(unsigned n_points, const uint64_t* point
     uint4* hi = (uint4*)ss.get((size_t)n_points * nhi * 32);
     if (!lo || !hi) return PLK_ERR_OOM;
     OpenPoints pts = {};
-    for (unsigned k = 0; k < n_points; ++k) put_words8(pts.x[k], points + (size_t)k * 4);
-    put_words8(pts.v, v);
+    for (unsigned k = 0; k < n_points; ++k) limbs_to_words(pts.x[k], points + (size_t)k * 4);
+    limbs_to_words(pts.v, v);
     const size_t lanes = (OPEN_LO + nhi) * n_points;
     k_open_pow_tables<P><<<(unsigned)((lanes + OPEN_LANES - 1) / OPEN_LANES), OPEN_LANES, 0, stream>>>(pts, (int)n_points, nhi, lo, hi);
     k_open_two_level<P><<<(unsigned)((degree + OPEN_LANES - 1) / OPEN_LANES), OPEN_LANES, 0, stream>>>(lo, hi, (int)n_points, OPEN_LO, nhi, degree, (uint4*)d_out);
@@ -377,7 +363,7 @@ template <class P> static int halo_s_t(unsigned k, const uint64_t* us, void* d_o
     uint4* uinv = (uint4*)ss.get((size_t)OPEN_MAX_US * 32);
     if (!lo || !hi || !uinv) return PLK_ERR_OOM;  // scratch_acquire has set the error text
     OpenUs arg = {};
-    for (unsigned j = 0; j < k; ++j) put_words8(arg.u[j], us + (size_t)j * 4);
+    for (unsigned j = 0; j < k; ++j) limbs_to_words(arg.u[j], us + (size_t)j * 4);
     k_halo_s_inverses<P><<<1, 64, 0, stream>>>(arg, k, uinv);
     k_halo_s_tables<P><<<(unsigned)((nlo + nhi + OPEN_LANES - 1) / OPEN_LANES), OPEN_LANES, 0, stream>>>(arg, uinv, k, nlo, nhi, lo, hi);
     // element i = lo[i & 1023] hi[i >> 10]: nlo = 2^k below 2^10 elements, where i >> 10 = 0 and i & 1023 = i
@@ -387,15 +373,8 @@ template <class P> static int halo_s_t(unsigned k, const uint64_t* us, void* d_o
     return PLK_OK;
 }
 
-#define PLK_OPEN_DISPATCH(field, CALL)                                                                  \
-    switch (field) {                                                                                    \
-        case PLK_FIELD_TWEEDLEDEE_BASE: return CALL(TweedledeeBaseParams);                              \
-        case PLK_FIELD_TWEEDLEDUM_BASE: return CALL(TweedledumBaseParams);                              \
-        case PLK_FIELD_BLS12_377_SCALAR: return CALL(Bls12377ScalarParams);                             \
-        case PLK_FIELD_PALLAS_BASE: return CALL(PallasBaseParams);                                      \
-        case PLK_FIELD_VESTA_BASE: return CALL(VestaBaseParams);                                        \
-    }                                                                                                   \
-    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field)
+// dispatch of the entry points below: every one has passed check_field, which gives the id's error first, as the callers expect
+template <class F> static int open_dispatch(int field, F&& f) { return or_invalid(with_field4(field, f), "field %d is not a 4-limb field", field); }
 
 static int check_field(int field) {
     if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
@@ -411,9 +390,7 @@ int plonk_eval_polys_dev_impl(int field, unsigned n_polys, const void* const* d_
     if (n_polys == 0) return PLK_OK;
     if (!d_out) return set_error(PLK_ERR_INVALID_ARG, "null pointer: output");
     PLK_TRY(ensure_device());
-#define CALL(P) eval_polys_t<P>(n_polys, d_polys, lens, n_points, points, d_out, stream)
-    PLK_OPEN_DISPATCH(field, CALL);
-#undef CALL
+    return open_dispatch(field, [&](auto t) { return eval_polys_t<tag_t<decltype(t)>>(n_polys, d_polys, lens, n_points, points, d_out, stream); });
 }
 
 int poly_reduce_dev_impl(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, const uint64_t* scalars, size_t degree, void* d_out,
@@ -426,9 +403,7 @@ int poly_reduce_dev_impl(int field, unsigned n_polys, const void* const* d_polys
     if (degree == 0) return PLK_OK;
     if (!d_out) return set_error(PLK_ERR_INVALID_ARG, "null pointer: output");
     PLK_TRY(ensure_device());
-#define CALL(P) poly_reduce_t<P>(n_polys, d_polys, lens, scalars, degree, d_out, stream)
-    PLK_OPEN_DISPATCH(field, CALL);
-#undef CALL
+    return open_dispatch(field, [&](auto t) { return poly_reduce_t<tag_t<decltype(t)>>(n_polys, d_polys, lens, scalars, degree, d_out, stream); });
 }
 
 int halo_build_b_dev_impl(int field, unsigned n_points, const uint64_t* points, const uint64_t* v, size_t degree, void* d_out, hipStream_t stream) {
@@ -438,9 +413,7 @@ int halo_build_b_dev_impl(int field, unsigned n_points, const uint64_t* points, 
     if (degree == 0) return PLK_OK;
     if (!d_out) return set_error(PLK_ERR_INVALID_ARG, "null pointer: output");
     PLK_TRY(ensure_device());
-#define CALL(P) build_b_t<P>(n_points, points, v, degree, d_out, stream)
-    PLK_OPEN_DISPATCH(field, CALL);
-#undef CALL
+    return open_dispatch(field, [&](auto t) { return build_b_t<tag_t<decltype(t)>>(n_points, points, v, degree, d_out, stream); });
 }
 
 int halo_s_dev_impl(int field, unsigned k, const uint64_t* us, void* d_out, hipStream_t stream) {
@@ -451,9 +424,7 @@ int halo_s_dev_impl(int field, unsigned k, const uint64_t* us, void* d_out, hipS
         if (!(us[4 * j] | us[4 * j + 1] | us[4 * j + 2] | us[4 * j + 3]))
             return set_error(PLK_ERR_INVALID_ARG, "No inverse: challenge %u is zero (field.rs:266, from plonk_util.rs:314)", j);
     PLK_TRY(ensure_device());
-#define CALL(P) halo_s_t<P>(k, us, d_out, stream)
-    PLK_OPEN_DISPATCH(field, CALL);
-#undef CALL
+    return open_dispatch(field, [&](auto t) { return halo_s_t<tag_t<decltype(t)>>(k, us, d_out, stream); });
 }
 
 }  // namespace plk

@@ -759,13 +759,6 @@ __global__ void __launch_bounds__(128) k_all_constraints(const uint4* __restrict
     for (int t = 0; t < NUM_TERMS; ++t) fe_store<P>(out + (i * NUM_TERMS + t) * 2, lz_to_rform<P>(u[t].rs()));
 }
 
-static void put_words(uint32_t (&dst)[8], const uint64_t* src) {
-    for (int i = 0; i < 4; ++i) {
-        dst[2 * i] = (uint32_t)src[i];
-        dst[2 * i + 1] = (uint32_t)(src[i] >> 32);
-    }
-}
-
 template <class P>
 static int vanishing_points_t(unsigned log_degree, const void* d_constants, const void* d_wires, const void* d_s_sigma, const void* d_z, const PlonkScalars& sc,
                               void* d_out, hipStream_t stream) {
@@ -815,12 +808,12 @@ static int fill_scalars(PlonkScalars& sc, const uint64_t* k_is, const uint64_t* 
                         const uint64_t* a) {
     if (!zeta || !a) return set_error(PLK_ERR_INVALID_ARG, "null InnerC constant");
     static const uint64_t zero4[4] = {0, 0, 0, 0};
-    for (int j = 0; j < NUM_ROUTED_WIRES; ++j) put_words(sc.k_is[j], k_is ? k_is + 4 * j : zero4);
-    put_words(sc.alpha, alpha ? alpha : zero4);
-    put_words(sc.beta, beta ? beta : zero4);
-    put_words(sc.gamma, gamma ? gamma : zero4);
-    put_words(sc.zeta, zeta);
-    put_words(sc.a, a);
+    for (int j = 0; j < NUM_ROUTED_WIRES; ++j) limbs_to_words(sc.k_is[j], k_is ? k_is + 4 * j : zero4);
+    limbs_to_words(sc.alpha, alpha ? alpha : zero4);
+    limbs_to_words(sc.beta, beta ? beta : zero4);
+    limbs_to_words(sc.gamma, gamma ? gamma : zero4);
+    limbs_to_words(sc.zeta, zeta);
+    limbs_to_words(sc.a, a);
     return PLK_OK;
 }
 
@@ -833,14 +826,8 @@ int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* 
     PLK_TRY(ensure_device());
     PlonkScalars sc;
     PLK_TRY(fill_scalars(sc, k_is, alpha, beta, gamma, inner_zeta, inner_a));
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return vanishing_points_t<TweedledeeBaseParams>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return vanishing_points_t<TweedledumBaseParams>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return vanishing_points_t<Bls12377ScalarParams>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream);
-        case PLK_FIELD_PALLAS_BASE: return vanishing_points_t<PallasBaseParams>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream);
-        case PLK_FIELD_VESTA_BASE: return vanishing_points_t<VestaBaseParams>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    return or_invalid(with_field4(field, [&](auto t) { return vanishing_points_t<tag_t<decltype(t)>>(log_degree, d_constants, d_wires, d_s_sigma, d_z, sc, d_out, stream); }),
+                      "field %d is not a circuit scalar field", field);
 }
 
 template <class P>
@@ -861,14 +848,8 @@ int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_consta
     PLK_TRY(ensure_device());
     PlonkScalars sc;
     PLK_TRY(fill_scalars(sc, nullptr, nullptr, nullptr, nullptr, inner_zeta, inner_a));
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return all_constraints_t<TweedledeeBaseParams>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return all_constraints_t<TweedledumBaseParams>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return all_constraints_t<Bls12377ScalarParams>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream);
-        case PLK_FIELD_PALLAS_BASE: return all_constraints_t<PallasBaseParams>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream);
-        case PLK_FIELD_VESTA_BASE: return all_constraints_t<VestaBaseParams>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    return or_invalid(with_field4(field, [&](auto t) { return all_constraints_t<tag_t<decltype(t)>>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream); }),
+                      "field %d is not a circuit scalar field", field);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1070,14 +1051,8 @@ int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_w
     static const uint64_t zero4[4] = {0, 0, 0, 0};
     PlonkScalars sc;
     PLK_TRY(fill_scalars(sc, k_is, nullptr, beta, gamma, zero4, zero4));
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return permutation_z_t<TweedledeeBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return permutation_z_t<TweedledumBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return permutation_z_t<Bls12377ScalarParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
-        case PLK_FIELD_PALLAS_BASE: return permutation_z_t<PallasBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
-        case PLK_FIELD_VESTA_BASE: return permutation_z_t<VestaBaseParams>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    return or_invalid(with_field4(field, [&](auto t) { return permutation_z_t<tag_t<decltype(t)>>(log_degree, d_wires, d_s_sigma, sigma_stride, sc, d_out, d_status, stream); }),
+                      "field %d is not a circuit scalar field", field);
 }
 
 }  // namespace plk

@@ -251,14 +251,8 @@ int poly_divide_by_z_h_dev_impl(int field, const void* d_coeffs, size_t len, siz
     if ((len && !d_coeffs) || (out_cap && !d_out)) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     if (n == 0) return set_error(PLK_ERR_INVALID_ARG, "Z_H = X^0 - 1 is zero");
     PLK_TRY(ensure_device());
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return divide_by_z_h_t<TweedledeeBaseParams>(d_coeffs, len, n, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return divide_by_z_h_t<TweedledumBaseParams>(d_coeffs, len, n, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return divide_by_z_h_t<Bls12377ScalarParams>(d_coeffs, len, n, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_PALLAS_BASE: return divide_by_z_h_t<PallasBaseParams>(d_coeffs, len, n, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_VESTA_BASE: return divide_by_z_h_t<VestaBaseParams>(d_coeffs, len, n, d_out, out_cap, out_len, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d has no NTT entry point", field);
+    return or_invalid(with_field4(field, [&](auto t) { return divide_by_z_h_t<tag_t<decltype(t)>>(d_coeffs, len, n, d_out, out_cap, out_len, stream); }),
+                      "field %d has no NTT entry point", field);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -313,14 +307,8 @@ int poly_mul_dev_impl(int field, const void* d_a, size_t la, const void* d_b, si
     if (!out_len) return set_error(PLK_ERR_INVALID_ARG, "null out_len");
     if ((la && !d_a) || (lb && !d_b) || !d_out) return set_error(PLK_ERR_INVALID_ARG, "null device pointer");
     PLK_TRY(ensure_device());
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return poly_mul_t<TweedledeeBaseParams>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return poly_mul_t<TweedledumBaseParams>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_BLS12_377_SCALAR: return poly_mul_t<Bls12377ScalarParams>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_PALLAS_BASE: return poly_mul_t<PallasBaseParams>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream);
-        case PLK_FIELD_VESTA_BASE: return poly_mul_t<VestaBaseParams>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream);
-    }
-    return set_error(PLK_ERR_INVALID_ARG, "field %d has no NTT entry point", field);
+    return or_invalid(with_field4(field, [&](auto t) { return poly_mul_t<tag_t<decltype(t)>>(d_a, la, d_b, lb, d_out, out_cap, out_len, stream); }),
+                      "field %d has no NTT entry point", field);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -43,12 +43,6 @@ struct PdivArg {  // host words of the call: -b' (R-form, zeros above k) and the
 int host_pdiv_prepare(int field, const uint64_t* b, size_t lb, uint64_t* negb, uint64_t* factor);
 int host_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out);
 
-template <class P> PLK_DI Fe<P> pdiv_words8(const uint32_t* w) {
-    Fe<P> r;
-#pragma unroll
-    for (int i = 0; i < P::NL; ++i) r.v[i] = w[i];
-    return r;
-}
 template <class P> PLK_DI Fz<P> pdiv_shfl(const Fz<P>& v, int src) {
     Fz<P> r;
 #pragma unroll
@@ -63,9 +57,9 @@ __global__ void __launch_bounds__(PDIV_MAX_K* PDIV_MAX_K) k_pdiv_table(PdivArg a
     constexpr int W = P::NL / 4;
     extern __shared__ uint4 s_m[];  // kp * kp entries, sized by the launch
     const int tid = threadIdx.x, i = tid & (kp - 1), j = tid / kp;
-    const Fe<P> nb = i < k ? to_rprime<P>(pdiv_words8<P>(arg.negb[i])) : fe_zero<P>();
+    const Fe<P> nb = i < k ? to_rprime<P>(fe_from_words<P>(arg.negb[i])) : fe_zero<P>();
     if (j == 0) limbs_store<P>(negb_tab, i, fz_from_fe<P>(nb));
-    if (tid == 0) limbs_store<P>(factor_tab, 0, fz_from_fe<P>(to_rprime<P>(pdiv_words8<P>(arg.factor))));
+    if (tid == 0) limbs_store<P>(factor_tab, 0, fz_from_fe<P>(to_rprime<P>(fe_from_words<P>(arg.factor))));
     Fe<P> e = pdiv_companion_entry<P>(i, j, k, nb);
     fe_store<P>(s_m + tid * W, e);
     __syncthreads();
@@ -206,15 +200,8 @@ static int poly_division_t(const uint64_t* negb, const uint64_t* factor, int k, 
     uint4* block_in = (uint4*)ss.get(nblk * kp * 32);
     if (!negb_tab || !factor_tab || !t_s || !t_sb || !rho || !states || !totals || !block_in) return PLK_ERR_OOM;  // scratch_acquire has set the error text
     PdivArg arg = {};
-    for (int i = 0; i < k; ++i)
-        for (int w = 0; w < 4; ++w) {
-            arg.negb[i][2 * w] = (uint32_t)negb[4 * i + w];
-            arg.negb[i][2 * w + 1] = (uint32_t)(negb[4 * i + w] >> 32);
-        }
-    for (int w = 0; w < 4; ++w) {
-        arg.factor[2 * w] = (uint32_t)factor[w];
-        arg.factor[2 * w + 1] = (uint32_t)(factor[w] >> 32);
-    }
+    for (int i = 0; i < k; ++i) limbs_to_words(arg.negb[i], negb + 4 * i);
+    limbs_to_words(arg.factor, factor);
     if (k > PDIV_LAZY_MAX_K) pdiv_launch<P, true>(arg, k, kp, d_a, la, d_q, q_len, d_rem, negb_tab, factor_tab, t_s, t_sb, rho, states, totals, block_in, stream);
     else pdiv_launch<P, false>(arg, k, kp, d_a, la, d_q, q_len, d_rem, negb_tab, factor_tab, t_s, t_sb, rho, states, totals, block_in, stream);
     hipError_t e = hipGetLastError();
@@ -250,16 +237,8 @@ int poly_division_dev_impl(int field, const void* d_a, size_t la, const uint64_t
     uint64_t negb[PDIV_MAX_K * 4] = {}, factor[4];
     if (host_pdiv_prepare(field, b, lb, negb, factor) != 0) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
     PLK_TRY(ensure_device());
-#define CALL(P) poly_division_t<P>(negb, factor, k, d_a, la, d_q, q_len, d_rem, stream)
-    switch (field) {
-        case PLK_FIELD_TWEEDLEDEE_BASE: return CALL(TweedledeeBaseParams);
-        case PLK_FIELD_TWEEDLEDUM_BASE: return CALL(TweedledumBaseParams);
-        case PLK_FIELD_BLS12_377_SCALAR: return CALL(Bls12377ScalarParams);
-        case PLK_FIELD_PALLAS_BASE: return CALL(PallasBaseParams);
-        case PLK_FIELD_VESTA_BASE: return CALL(VestaBaseParams);
-    }
-#undef CALL
-    return set_error(PLK_ERR_INVALID_ARG, "field %d is not a 4-limb field", field);
+    return or_invalid(with_field4(field, [&](auto t) { return poly_division_t<tag_t<decltype(t)>>(negb, factor, k, d_a, la, d_q, q_len, d_rem, stream); }),
+                      "field %d is not a 4-limb field", field);
 }
 
 int poly_from_roots_impl(int field, unsigned k, const uint64_t* roots, uint64_t* out) {

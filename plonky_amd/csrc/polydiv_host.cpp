@@ -3,6 +3,7 @@
 // prod (X - s_i) of the public-input denominator (plonk.rs:207-215), at most k^2 / 2 products for k <= 32 roots.
 #include <cstring>
 
+#include "dispatch.cuh"
 #include "fp.cuh"
 
 namespace plk {
@@ -42,24 +43,18 @@ template <class P> static void from_roots_t(unsigned k, const uint64_t* roots, u
 
 // field: PLK_FIELD_* (include/plonky_hip.h), the five 4-limb fields.  Return 0, or -1 for another field.
 int host_pdiv_prepare(int field, const uint64_t* b, size_t lb, uint64_t* negb, uint64_t* factor) {
-    switch (field) {
-        case 0: prepare_t<TweedledeeBaseParams>(b, lb, negb, factor); return 0;
-        case 1: prepare_t<TweedledumBaseParams>(b, lb, negb, factor); return 0;
-        case 2: prepare_t<Bls12377ScalarParams>(b, lb, negb, factor); return 0;
-        case 4: prepare_t<PallasBaseParams>(b, lb, negb, factor); return 0;
-        case 5: prepare_t<VestaBaseParams>(b, lb, negb, factor); return 0;
-    }
-    return -1;
+    const int rc = with_field4(field, [&](auto t) {
+        prepare_t<tag_t<decltype(t)>>(b, lb, negb, factor);
+        return 0;
+    });
+    return rc == PLK_NO_MATCH ? -1 : rc;
 }
 int host_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out) {
-    switch (field) {
-        case 0: from_roots_t<TweedledeeBaseParams>(k, roots, out); return 0;
-        case 1: from_roots_t<TweedledumBaseParams>(k, roots, out); return 0;
-        case 2: from_roots_t<Bls12377ScalarParams>(k, roots, out); return 0;
-        case 4: from_roots_t<PallasBaseParams>(k, roots, out); return 0;
-        case 5: from_roots_t<VestaBaseParams>(k, roots, out); return 0;
-    }
-    return -1;
+    const int rc = with_field4(field, [&](auto t) {
+        from_roots_t<tag_t<decltype(t)>>(k, roots, out);
+        return 0;
+    });
+    return rc == PLK_NO_MATCH ? -1 : rc;
 }
 
 }  // namespace plk

@@ -8,6 +8,7 @@
 // Records are fixed size: BYTES per field element (32, or 48 for Bls12377Base), 1 + BYTES per point (the reference's reader
 // stops after the mask byte of the identity; a record here simply leaves the rest unused).
 #include "common.h"
+#include "ec.cuh"
 #include "fp.cuh"
 #include "tables.cuh"
 
@@ -163,21 +164,12 @@ __global__ void __launch_bounds__(64) k_point_from_bytes(const uint8_t* __restri
 int field_bytes_impl(int field, int from_bytes, const void* d_in, size_t count, void* d_out, unsigned* d_bad, hipStream_t stream) {
     if (count == 0) return PLK_OK;
     const unsigned blocks = (unsigned)((count + 127) / 128);
-    switch (field) {
-#define CASE(ID, P)                                                                                                   \
-    case ID:                                                                                                          \
-        if (from_bytes) k_field_from_bytes<P><<<blocks, 128, 0, stream>>>((const uint8_t*)d_in, count, (uint4*)d_out, d_bad); \
-        else k_field_to_bytes<P><<<blocks, 128, 0, stream>>>((const uint4*)d_in, count, (uint8_t*)d_out);             \
-        break;
-        CASE(PLK_FIELD_TWEEDLEDEE_BASE, TweedledeeBaseParams)
-        CASE(PLK_FIELD_TWEEDLEDUM_BASE, TweedledumBaseParams)
-        CASE(PLK_FIELD_BLS12_377_SCALAR, Bls12377ScalarParams)
-        CASE(PLK_FIELD_BLS12_377_BASE, Bls12377BaseParams)
-        CASE(PLK_FIELD_PALLAS_BASE, PallasBaseParams)
-        CASE(PLK_FIELD_VESTA_BASE, VestaBaseParams)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
-    }
+    PLK_TRY(or_bad_field(with_field(field, [&](auto t) {
+        using P = tag_t<decltype(t)>;
+        if (from_bytes) k_field_from_bytes<P><<<blocks, 128, 0, stream>>>((const uint8_t*)d_in, count, (uint4*)d_out, d_bad);
+        else k_field_to_bytes<P><<<blocks, 128, 0, stream>>>((const uint4*)d_in, count, (uint8_t*)d_out);
+        return PLK_OK;
+    }), field));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -189,23 +181,15 @@ static uint32_t curve_b(int curve) { return curve == PLK_CURVE_TWEEDLEDUM ? 7u :
 int point_bytes_impl(int curve, int from_bytes, const void* d_in, const void* d_zero, size_t count, void* d_out, void* d_out_zero, void* d_status,
                      hipStream_t stream) {
     if (count == 0) return PLK_OK;
-    switch (curve) {
-#define CASE(ID, P)                                                                                                               \
-    case ID:                                                                                                                      \
-        if (from_bytes)                                                                                                           \
-            k_point_from_bytes<P><<<(unsigned)((count + 63) / 64), 64, 0, stream>>>((const uint8_t*)d_in, count, curve_b(curve), (uint4*)d_out, \
-                                                                                   (uint8_t*)d_out_zero, (uint8_t*)d_status);    \
-        else                                                                                                                      \
-            k_point_to_bytes<P><<<(unsigned)((count + 127) / 128), 128, 0, stream>>>((const uint4*)d_in, (const uint8_t*)d_zero, count, (uint8_t*)d_out); \
-        break;
-        CASE(PLK_CURVE_TWEEDLEDEE, TweedledeeBaseParams)
-        CASE(PLK_CURVE_TWEEDLEDUM, TweedledumBaseParams)
-        CASE(PLK_CURVE_BLS12_377, Bls12377BaseParams)
-        CASE(PLK_CURVE_PALLAS, PallasBaseParams)
-        CASE(PLK_CURVE_VESTA, VestaBaseParams)
-#undef CASE
-        default: return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
-    }
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using P = typename tag_t<decltype(t)>::FP;
+        if (from_bytes)
+            k_point_from_bytes<P><<<(unsigned)((count + 63) / 64), 64, 0, stream>>>((const uint8_t*)d_in, count, curve_b(curve), (uint4*)d_out,
+                                                                                   (uint8_t*)d_out_zero, (uint8_t*)d_status);
+        else
+            k_point_to_bytes<P><<<(unsigned)((count + 127) / 128), 128, 0, stream>>>((const uint4*)d_in, (const uint8_t*)d_zero, count, (uint8_t*)d_out);
+        return PLK_OK;
+    }), curve));
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
