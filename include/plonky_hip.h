@@ -229,6 +229,36 @@ int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wire
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out);
 
+/* ---- the Plookup prover  (plookup/src/plookup.rs) ------------------------------------------------------------------------------- */
+/* The two O(n) loops of `prove` that no other entry point covers.  N = 2^log_size = n + 1 is the order of the subgroup H.  These four
+ * entries take the SIZE first and the field id second: the id-first entries form a pinned set, and these were added after it.  Fields:
+ * the 4-limb circuit scalar fields, any other id is PLK_ERR_INVALID_ARG.  Elements are the reference's stored form (Montgomery,
+ * canonical); beta, gamma, alpha are host arrays of 4 limbs.  The _dev forms are asynchronous on `stream`, do not synchronise, leave
+ * their inputs unchanged and take their working memory from the scratch pool.
+ * grand_polynomial (plookup.rs:180-202).  d_f: N elements, the prover's f_padded (element N - 1 is not read); d_t: N; d_s: 2 N - 1, the
+ * sorted multiset (h1 = s[..N], h2 = s[n..]).  d_out: N elements, out[0] = 1, out[i] = prod_(j < i) r_j for i <= n - 1, out[n] = 1 (the
+ * reference pushes ONE there without computing it), with
+ *   r_j = b1 (gamma + f_j) (gamma b1 + t_j + beta t_(j+1)) / [(gamma b1 + s_j + beta s_(j+1)) (gamma b1 + s_(n+j) + beta s_(n+j+1))],  b1 = beta + 1.
+ * 1 <= log_size <= 28 (0 is PLK_ERR_INVALID_ARG: the reference reads f[0]).  d_status (nullable, device, 2 x uint32, written in stream
+ * order): [0] = zero denominators among rows 0..n-2 (the output is unspecified when > 0), [1] = 1 iff no row 0..n-1 had a zero
+ * denominator and the product of r_j over j < n is 1 - the statement that the argument holds, the value the reference hard-codes. */
+int plk_plookup_grand_product_dev(unsigned log_size, int field, const void* d_f, const void* d_t, const void* d_s, const uint64_t* beta,
+                                  const uint64_t* gamma, void* d_out, void* d_status, void* stream);
+/* Same with host pointers; PLK_ERR_INVALID_ARG with plk_last_error() starting "No inverse" where the reference's division panics (a zero
+ * denominator in rows 0..n-2).  closes (nullable): status word [1] above. */
+int plk_plookup_grand_product(unsigned log_size, int field, const uint64_t* f, const uint64_t* t, const uint64_t* s, const uint64_t* beta,
+                              const uint64_t* gamma, uint64_t* out, int* closes);
+/* The 4N-point loop of vanishing_polynomial (plookup.rs:225-269).  d_values_4n: [5][4N] row-major, rows z, f, t, h1, h2 - the LDEs of
+ * plookup.rs:219-223 (plk_ntt_padded_dev).  d_out: 4N elements, reduce_with_powers of the four terms of plookup.rs:232-246 at x = g4^i;
+ * the closing Polynomial::from_evaluations is plk_ntt_dev(inverse = 1).  eval_l_i (plookup.rs:275-282) returns ZERO at its own basis
+ * point, so both Lagrange factors are 0 at every i = 0 (mod 4): reproduced.  1 <= log_size, log_size + 2 <= 30.  The first call for a
+ * (field, log_size) builds and caches the tables (powers of g4, L_0 over the domain); plk_ntt_clear_cache drops them. */
+int plk_plookup_vanishing_points_dev(unsigned log_size, int field, const void* d_values_4n, const uint64_t* alpha, const uint64_t* beta,
+                                     const uint64_t* gamma, void* d_out, void* stream);
+/* Same with a host table (copied through PCIe). */
+int plk_plookup_vanishing_points(unsigned log_size, int field, const uint64_t* values_4n, const uint64_t* alpha, const uint64_t* beta,
+                                 const uint64_t* gamma, uint64_t* out);
+
 /* ---- the opening step  (src/plonk.rs:261-308, src/halo.rs:38-44 and 143-155, src/plonk_util.rs:123-133 and 311-326) ------------- */
 /* Everything between the commitments and the first round of the inner-product argument.  All of it is exact field arithmetic, so
  * every output is the reference's word for word.  The _dev forms are asynchronous on `stream`, do not synchronise, leave their

@@ -545,6 +545,58 @@ def permutation_polynomial(field, degree, wire_values, s_sigma_values, k_is, bet
     return out
 
 
+# ---- the Plookup prover's two loops (plookup/src/plookup.rs) ----
+def plookup_sorted_multiset(f, t):
+    """`s` of the Plookup protocol: f ++ t sorted by t, as sort_by orders it (plookup.rs:171-177, a stable sort on the position of
+    an element's FIRST occurrence in t).  f: (n, 4), t: (n + 1, 4) limb arrays -> (2 n + 1, 4).  An element of f that is not in t makes
+    the reference's unwrap() panic -> AssertionError here.  Host only: the sort stays on the host."""
+    fa, ta = _elems(0, f), _elems(0, t)
+    pos = {}
+    for i, row in enumerate(ta):
+        pos.setdefault(row.tobytes(), i)
+    s = np.concatenate([fa, ta])
+    try:
+        keys = np.fromiter((pos[row.tobytes()] for row in s), dtype=np.int64, count=s.shape[0])
+    except KeyError:
+        raise AssertionError("called `Option::unwrap()` on a `None` value: an element of f is not in t")
+    return np.ascontiguousarray(s[np.argsort(keys, kind="stable")])
+
+
+def plookup_grand_polynomial(field, f, t, s, beta, gamma, return_closes=False):
+    """grand_polynomial (plookup.rs:180-202): f (N, 4) = f_padded (or the n = N - 1 values the reference passes: the last row is not
+    read), t (N, 4), s (2 N - 1, 4) -> the N values of Z, values[0] = values[N - 1] = 1.  A zero denominator in rows 0..n-2 panics in
+    the reference ("No inverse") -> AssertionError.  return_closes: also whether the product over all n rows is 1 (f is in t)."""
+    ta = _elems(field, t)
+    size = ta.shape[0]
+    log_size = log2_strict(size)
+    fa = _elems(field, f)
+    assert fa.shape[0] in (size - 1, size), "f has n or n + 1 rows"
+    if fa.shape[0] == size - 1:
+        fa = np.concatenate([fa, np.zeros((1, 4), dtype=np.uint64)])
+    sa = _elems(field, s)
+    assert sa.shape[0] == 2 * size - 1, "s has 2 n + 1 rows"
+    b, g = (np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma))
+    out = np.empty((size, 4), dtype=np.uint64)
+    closes = ctypes.c_int(0)
+    rc = _lib.load().plk_plookup_grand_product(log_size, field, _ptr(fa), _ptr(ta), _ptr(sa), _ptr(b), _ptr(g), _ptr(out), ctypes.byref(closes))
+    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
+        raise AssertionError("No inverse")  # the reference panics (plookup.rs:191, field.rs Div)
+    _lib.check(rc)
+    return (out, bool(closes.value)) if return_closes else out
+
+
+def plookup_vanishing_values(field, values_4n, alpha, beta, gamma):
+    """The 4(n+1)-point loop of vanishing_polynomial (plookup.rs:225-269): values_4n (5, 4 N, 4), rows z, f, t, h1, h2 on the 4N domain
+    -> (4 N, 4); Polynomial::from_evaluations of the result is the vanishing polynomial."""
+    v = np.ascontiguousarray(values_4n, dtype=np.uint64)
+    assert v.ndim == 3 and v.shape[0] == 5 and v.shape[2] == 4
+    log_size = log2_strict(v.shape[1]) - 2
+    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma)]
+    out = np.empty((v.shape[1], 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_plookup_vanishing_points(log_size, field, _ptr(v), *[_ptr(x) for x in sc], _ptr(out)))
+    return out
+
+
 # ---- the opening step (plonk.rs:261-308, halo.rs:38-44 and 143-155, plonk_util.rs:123-133 and 311-326) ----
 def _poly_args(polys):
     """list of (len, 4) limb arrays -> (kept arrays, ctypes array of host pointers, lengths)"""

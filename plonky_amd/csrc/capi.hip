@@ -803,6 +803,68 @@ int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wire
     if (wraps_to_one) *wraps_to_one = (int)st[1];
     return c.finish();
 }
+// ---- the Plookup prover's two loops (plookup.hip): the size comes first, the field id second ----
+int plk_plookup_grand_product_dev(unsigned log_size, int field, const void* d_f, const void* d_t, const void* d_s, const uint64_t* beta,
+                                  const uint64_t* gamma, void* d_out, void* d_status, void* stream) {
+    PLK_API;
+    return plookup_grand_product_dev_impl(log_size, field, d_f, d_t, d_s, beta, gamma, d_out, d_status, as_stream(stream));
+}
+int plk_plookup_grand_product(unsigned log_size, int field, const uint64_t* f, const uint64_t* t, const uint64_t* s, const uint64_t* beta,
+                              const uint64_t* gamma, uint64_t* out, int* closes) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    if (log_size == 0) return set_error(PLK_ERR_INVALID_ARG, "log_size 0: the grand product reads f[0] (plookup.rs:187)");
+    if (log_size > 28) return set_error(PLK_ERR_TWO_ADICITY, "log_size %u too large", log_size);
+    if (!f || !t || !s || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t N = (size_t)1 << log_size, row = N * 32;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(f, row);
+    c.pin(t, row);
+    c.pin(s, 2 * row - 32);
+    c.pin(out, row);
+    void *df = nullptr, *dt = nullptr, *ds = nullptr, *dout = nullptr, *dst = nullptr;
+    PLK_TRY(c.in(df, f, row));
+    PLK_TRY(c.in(dt, t, row));
+    PLK_TRY(c.in(ds, s, 2 * row - 32));
+    PLK_TRY(c.tmp(dout, row));
+    PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
+    PLK_TRY(plookup_grand_product_dev_impl(log_size, field, df, dt, ds, beta, gamma, dout, dst, c.stream()));
+    uint32_t st[2] = {0, 0};
+    PLK_TRY(c.out(st, dst, sizeof(st)));
+    PLK_TRY(c.sync());
+    if (st[0]) {
+        c.done = true;
+        return set_error(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plookup.rs:191)", st[0]);
+    }
+    PLK_TRY(c.out(out, dout, row));
+    if (closes) *closes = (int)st[1];
+    return c.finish();
+}
+int plk_plookup_vanishing_points_dev(unsigned log_size, int field, const void* d_values_4n, const uint64_t* alpha, const uint64_t* beta,
+                                     const uint64_t* gamma, void* d_out, void* stream) {
+    PLK_API;
+    return plookup_vanishing_points_dev_impl(log_size, field, d_values_4n, alpha, beta, gamma, d_out, as_stream(stream));
+}
+int plk_plookup_vanishing_points(unsigned log_size, int field, const uint64_t* values_4n, const uint64_t* alpha, const uint64_t* beta,
+                                 const uint64_t* gamma, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d is not a circuit scalar field", field);
+    if (log_size == 0) return set_error(PLK_ERR_INVALID_ARG, "log_size 0: the prover pads to n + 1 >= 2 rows");
+    if (log_size + 2 > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_size %u too large", log_size);
+    if (!values_4n || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t row = ((size_t)4 << log_size) * 32;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(values_4n, 5 * row);
+    c.pin(out, row);
+    void *dv = nullptr, *dout = nullptr;
+    PLK_TRY(c.in(dv, values_4n, 5 * row));
+    PLK_TRY(c.tmp(dout, row));
+    PLK_TRY(plookup_vanishing_points_dev_impl(log_size, field, dv, alpha, beta, gamma, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, row));
+    return c.finish();
+}
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out) {
     PLK_API;

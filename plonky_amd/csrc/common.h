@@ -165,6 +165,7 @@ int ntt_dev_hooked_impl(int field, unsigned log_n, int inverse, unsigned batch, 
 int ntt_plan_pow_table(int field, unsigned log_n, const void** pw, int* log_t, std::shared_ptr<const void>* hold = nullptr);
 int ntt_reference_table_dev_impl(int field, unsigned log_n, void* d_out, hipStream_t stream);
 int plonk_clear_cache_impl();
+void plookup_clear_cache();  // the Plookup tables (plookup.hip); plonk_clear_cache_impl drops them with its own
 int field_inner_product_dev_impl(int field, const void* d_a, const void* d_b, size_t count, void* d_out, hipStream_t stream);
 int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, const uint64_t* s_lo, const uint64_t* s_hi, size_t count, void* d_out,
                                hipStream_t stream);
@@ -178,6 +179,11 @@ int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* 
                                     const uint64_t* inner_a, void* d_out, hipStream_t stream);
 int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
                                  const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, hipStream_t stream);
+// the Plookup prover's two loops (plookup.hip): size first, then the field id (include/plonky_hip.h says why)
+int plookup_grand_product_dev_impl(unsigned log_size, int field, const void* d_f, const void* d_t, const void* d_s, const uint64_t* beta, const uint64_t* gamma,
+                                   void* d_out, void* d_status, hipStream_t stream);
+int plookup_vanishing_points_dev_impl(unsigned log_size, int field, const void* d_values_4n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
+                                      void* d_out, hipStream_t stream);
 // the opening step (opening.hip): d_polys / lens are HOST arrays of n_polys device pointers / lengths, the scalars host limbs
 int plonk_eval_polys_dev_impl(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, unsigned n_points, const uint64_t* points, void* d_out,
                               hipStream_t stream);

@@ -212,6 +212,46 @@ def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k
     return (out, status) if want_status else out
 
 
+# ---- the Plookup prover's two loops on device-resident tables (plookup/src/plookup.rs) ----
+def plookup_grand_polynomial_dev(field, log_size, f, t, s, beta, gamma, out=None, status=False):
+    """grand_polynomial (plookup.rs:180-202): int64 CUDA tensors f (N, 4) (f_padded; the last row is not read), t (N, 4),
+    s (2 N - 1, 4), N = 2^log_size; beta, gamma host limbs.  Returns Z (N, 4); with status=True (or a (2,) int32 CUDA tensor) also the
+    status words, written in stream order: [0] zero denominators among rows 0..n-2 (Z unspecified when > 0), [1] 1 iff the product
+    over all n rows is 1."""
+    size = 1 << log_size
+    for x, rows in ((f, size), (t, size), (s, 2 * size - 1)):
+        assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.numel() == rows * 4
+    if out is None:
+        out = torch.empty((size, 4), dtype=torch.int64, device=f.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == size * 4
+    want_status = status is not None and status is not False
+    if status is True:
+        status = torch.empty(2, dtype=torch.int32, device=f.device)
+    if want_status:
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
+    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma)]
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().plk_plookup_grand_product_dev(log_size, field, ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                         ctypes.c_void_p(s.data_ptr()), *[p(x) for x in sc], ctypes.c_void_p(out.data_ptr()),
+                                                         ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
+    return (out, status) if want_status else out
+
+
+def plookup_vanishing_values_dev(field, log_size, values_4n, alpha, beta, gamma, out=None):
+    """The 4N-point loop of vanishing_polynomial (plookup.rs:225-269): values_4n an int64 CUDA tensor (5, 4 N, 4), rows z, f, t, h1, h2
+    (ntt_padded_dev to log_size + 2); the scalars are host limbs.  Returns (4 N, 4)."""
+    n4 = 4 << log_size
+    assert values_4n.is_cuda and values_4n.dtype == torch.int64 and values_4n.is_contiguous() and values_4n.numel() == 5 * n4 * 4
+    if out is None:
+        out = torch.empty((n4, 4), dtype=torch.int64, device=values_4n.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == n4 * 4
+    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma)]
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().plk_plookup_vanishing_points_dev(log_size, field, ctypes.c_void_p(values_4n.data_ptr()), *[p(x) for x in sc],
+                                                            ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
 # ---- the opening step on device-resident polynomials (plonk.rs:261-308, halo.rs:38-44, 143-155) ----
 def _poly_list(polys):
     """list of (len, 4) int64 CUDA tensors -> (ctypes array of device pointers, size_t lengths)"""
