@@ -230,7 +230,7 @@ int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* 
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out);
 
 /* ---- the Plookup prover  (plookup/src/plookup.rs) ------------------------------------------------------------------------------- */
-/* The two O(n) loops of `prove` that no other entry point covers.  N = 2^log_size = n + 1 is the order of the subgroup H.  These four
+/* The sort and the two O(n) loops of `prove` that no other entry point covers.  N = 2^log_size = n + 1 is the order of the subgroup H.  These six
  * entries take the SIZE first and the field id second: the id-first entries form a pinned set, and these were added after it.  Fields:
  * the 4-limb circuit scalar fields, any other id is PLK_ERR_INVALID_ARG.  Elements are the reference's stored form (Montgomery,
  * canonical); beta, gamma, alpha are host arrays of 4 limbs.  The _dev forms are asynchronous on `stream`, do not synchronise, leave
@@ -258,6 +258,19 @@ int plk_plookup_vanishing_points_dev(unsigned log_size, int field, const void* d
 /* Same with a host table (copied through PCIe). */
 int plk_plookup_vanishing_points(unsigned log_size, int field, const uint64_t* values_4n, const uint64_t* alpha, const uint64_t* beta,
                                  const uint64_t* gamma, uint64_t* out);
+/* The sorted multiset, the first line of `prove` (plookup.rs:20-22; sort_by, 171-177): s = f ++ t in the order of each value's FIRST
+ * occurrence in t.  Rows with the same key hold the same value, so s is t_i repeated c_i times for every row i of t that is the first
+ * of its value, c_i = #{j < n : f_j = t_i} + #{k < N : t_k = t_i}: a table over t, a histogram, an integer scan and an expansion, no
+ * field arithmetic and no comparison sort.  1 <= log_size <= 28, any other size and any id that is not a 4-limb field is
+ * PLK_ERR_INVALID_ARG.  d_f: N elements, the prover's f_padded (rows 0..n-1 are read, row N - 1 is not: the grand product's
+ * convention); d_t: N; d_s: 2 N - 1 elements out (h1 = s[..N], h2 = s[n..]).  Equality is equality of the 8 words of the stored form.
+ * d_status (nullable, device, 2 x uint32, written in stream order): [0] = rows of f (0..n-1) whose value is not in t - the reference's
+ * unwrap() panics there; [1] = distinct values in t.  When [0] > 0 the rows of s beyond the total count are written as zero; nothing
+ * outside d_s is touched.  s is unique: the output is bit-identical from run to run. */
+int plk_plookup_sorted_multiset_dev(unsigned log_size, int field, const void* d_f, const void* d_t, void* d_s, void* d_status, void* stream);
+/* Same with host pointers (copied through PCIe).  With rows of f outside t: PLK_ERR_INVALID_ARG, plk_last_error() starting
+ * "called `Option::unwrap()` on a `None` value", s not written.  missing (nullable): status word [0] above. */
+int plk_plookup_sorted_multiset(unsigned log_size, int field, const uint64_t* f, const uint64_t* t, uint64_t* s, unsigned* missing);
 
 /* ---- the opening step  (src/plonk.rs:261-308, src/halo.rs:38-44 and 143-155, src/plonk_util.rs:123-133 and 311-326) ------------- */
 /* Everything between the commitments and the first round of the inner-product argument.  All of it is exact field arithmetic, so
@@ -503,8 +516,8 @@ int plk_selftest_quad(int curve, const uint64_t* pts_xy, size_t n, unsigned quad
 
 /* ---- checked build --------------------------------------------------------------------------------- */
 /* libplonky_hip_checked.so (make -C plonky_amd/csrc checked) is the same library with -DPLK_CHECKED: every index the MSM's
- * ordering and accumulation kernels compute into their work arrays and tables is compared with its bound, a violation is
- * counted and the access skipped.  plk_checked_build() tells the two builds apart (1 / 0); plk_checked_failures() returns
+ * ordering and accumulation kernels compute into their work arrays and tables, and every index the Plookup sorted multiset reads
+ * from its table or finds by bisection (site 7), is compared with its bound, a violation is counted and the access skipped. plk_checked_build() tells the two builds apart (1 / 0); plk_checked_failures() returns
  * the violation counters per guarded site (counts[8]; all zero in the normal build, which has no guards). */
 int plk_checked_build(void);
 int plk_checked_failures(unsigned* counts);

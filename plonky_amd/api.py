@@ -562,6 +562,26 @@ def plookup_sorted_multiset(f, t):
     return np.ascontiguousarray(s[np.argsort(keys, kind="stable")])
 
 
+def plookup_sorted_multiset_device(field, f, t):
+    """plookup_sorted_multiset through the device (plk_plookup_sorted_multiset; host arrays, copied through PCIe): f (N, 4) = f_padded
+    or the n = N - 1 values the reference passes, t (N, 4), N a power of two >= 2 -> (2 N - 1, 4).  An element of f that is not in t
+    makes the reference's unwrap() panic -> AssertionError."""
+    ta = _elems(field, t)
+    size = ta.shape[0]
+    log_size = log2_strict(size)
+    fa = _elems(field, f)
+    assert fa.shape[0] in (size - 1, size), "f has n or n + 1 rows"
+    if fa.shape[0] == size - 1:
+        fa = np.concatenate([fa, np.zeros((1, 4), dtype=np.uint64)])
+    out = np.empty((2 * size - 1, 4), dtype=np.uint64)
+    missing = ctypes.c_uint(0)
+    rc = _lib.load().plk_plookup_sorted_multiset(log_size, field, _ptr(fa), _ptr(ta), _ptr(out), ctypes.byref(missing))
+    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("called `Option::unwrap()`"):
+        raise AssertionError("called `Option::unwrap()` on a `None` value: %d elements of f are not in t" % missing.value)
+    _lib.check(rc)
+    return out
+
+
 def plookup_grand_polynomial(field, f, t, s, beta, gamma, return_closes=False):
     """grand_polynomial (plookup.rs:180-202): f (N, 4) = f_padded (or the n = N - 1 values the reference passes: the last row is not
     read), t (N, 4), s (2 N - 1, 4) -> the N values of Z, values[0] = values[N - 1] = 1.  A zero denominator in rows 0..n-2 panics in

@@ -865,6 +865,38 @@ int plk_plookup_vanishing_points(unsigned log_size, int field, const uint64_t* v
     PLK_TRY(c.out(out, dout, row));
     return c.finish();
 }
+// ---- the Plookup sorted multiset (plookup_sort.hip) ----
+int plk_plookup_sorted_multiset_dev(unsigned log_size, int field, const void* d_f, const void* d_t, void* d_s, void* d_status, void* stream) {
+    PLK_API;
+    return plookup_sorted_multiset_dev_impl(log_size, field, d_f, d_t, d_s, d_status, as_stream(stream));
+}
+int plk_plookup_sorted_multiset(unsigned log_size, int field, const uint64_t* f, const uint64_t* t, uint64_t* s, unsigned* missing) {
+    PLK_API;
+    PLK_TRY(plookup_sorted_multiset_check(log_size, field));
+    if (!f || !t || !s) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t N = (size_t)1 << log_size, row = N * 32;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(f, row);
+    c.pin(t, row);
+    c.pin(s, 2 * row - 32);
+    void *df = nullptr, *dt = nullptr, *ds = nullptr, *dst = nullptr;
+    PLK_TRY(c.in(df, f, row));
+    PLK_TRY(c.in(dt, t, row));
+    PLK_TRY(c.tmp(ds, 2 * row - 32));
+    PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
+    PLK_TRY(plookup_sorted_multiset_dev_impl(log_size, field, df, dt, ds, dst, c.stream()));
+    uint32_t st[2] = {0, 0};
+    PLK_TRY(c.out(st, dst, sizeof(st)));
+    PLK_TRY(c.sync());
+    if (missing) *missing = st[0];
+    if (st[0]) {
+        c.done = true;
+        return set_error(PLK_ERR_INVALID_ARG, "called `Option::unwrap()` on a `None` value: %u rows of f are not in t (plookup.rs:173)", st[0]);
+    }
+    PLK_TRY(c.out(s, ds, 2 * row - 32));
+    return c.finish();
+}
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out) {
     PLK_API;

@@ -184,6 +184,9 @@ int plookup_grand_product_dev_impl(unsigned log_size, int field, const void* d_f
                                    void* d_out, void* d_status, hipStream_t stream);
 int plookup_vanishing_points_dev_impl(unsigned log_size, int field, const void* d_values_4n, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,
                                       void* d_out, hipStream_t stream);
+// the Plookup sorted multiset (plookup_sort.hip); the check holds the refusals the host entry shares
+int plookup_sorted_multiset_check(unsigned log_size, int field);
+int plookup_sorted_multiset_dev_impl(unsigned log_size, int field, const void* d_f, const void* d_t, void* d_s, void* d_status, hipStream_t stream);
 // the opening step (opening.hip): d_polys / lens are HOST arrays of n_polys device pointers / lengths, the scalars host limbs
 int plonk_eval_polys_dev_impl(int field, unsigned n_polys, const void* const* d_polys, const size_t* lens, unsigned n_points, const uint64_t* points, void* d_out,
                               hipStream_t stream);

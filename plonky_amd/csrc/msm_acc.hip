@@ -312,6 +312,7 @@ PLK_FOR_EACH_CURVE(PLK_ACC_INSTANTIATE)
 
 // ---- the checked build (-DPLK_CHECKED: msm_acc_checked.o + msm_order_checked.o; include/plonky_hip.h) ----
 int msm_order_checked_failures(unsigned* counts);  // msm_order.hip
+int plookup_sort_checked_failures(unsigned* counts);  // plookup_sort.hip
 PLK_CHK_READER(msm_acc_checked_failures)
 int checked_build_impl() {
 #ifdef PLK_CHECKED
@@ -331,6 +332,8 @@ int checked_failures_impl(unsigned* counts) {
     PLK_TRY(msm_acc_checked_failures(part));    // the accumulation kernel's guards
     for (int k = 0; k < 8; ++k) counts[k] += part[k];
     PLK_TRY(msm_order_checked_failures(part));  // the ordering kernels' guards
+    for (int k = 0; k < 8; ++k) counts[k] += part[k];
+    PLK_TRY(plookup_sort_checked_failures(part));  // the Plookup sort's guards (site 7)
     for (int k = 0; k < 8; ++k) counts[k] += part[k];
 #endif
     return PLK_OK;

@@ -252,6 +252,28 @@ def plookup_vanishing_values_dev(field, log_size, values_4n, alpha, beta, gamma,
     return out
 
 
+def plookup_sorted_multiset_dev(field, log_size, f, t, out=None, status=False):
+    """s of plookup.rs:20-22 (f ++ t in the order of each value's first occurrence in t): int64 CUDA tensors f (N, 4) (f_padded; the
+    last row is not read) and t (N, 4), N = 2^log_size.  Returns s (2 N - 1, 4), h1 = s[:N], h2 = s[N - 1:]; with status=True (or a
+    (2,) int32 CUDA tensor) also the status words, written in stream order: [0] rows of f whose value is not in t (the reference
+    panics; the rows of s beyond the total are zero then), [1] distinct values in t."""
+    size = 1 << log_size
+    for x in (f, t):
+        assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.numel() == size * 4
+    if out is None:
+        out = torch.empty((2 * size - 1, 4), dtype=torch.int64, device=f.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == (2 * size - 1) * 4
+    want_status = status is not None and status is not False
+    if status is True:
+        status = torch.empty(2, dtype=torch.int32, device=f.device)
+    if want_status:
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
+    _lib.check(_lib.load().plk_plookup_sorted_multiset_dev(log_size, field, ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                           ctypes.c_void_p(out.data_ptr()),
+                                                           ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
+    return (out, status) if want_status else out
+
+
 # ---- the opening step on device-resident polynomials (plonk.rs:261-308, halo.rs:38-44, 143-155) ----
 def _poly_list(polys):
     """list of (len, 4) int64 CUDA tensors -> (ctypes array of device pointers, size_t lengths)"""

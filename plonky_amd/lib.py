@@ -62,6 +62,8 @@ SYMBOLS = [
     ("plk_plookup_grand_product", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plookup_vanishing_points_dev", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plookup_vanishing_points", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_plookup_sorted_multiset_dev", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_plookup_sorted_multiset", _i, [_u, _i, _vp, _vp, _vp, _vp]),
     ("plk_field_powers_dev", _i, [_i, _vp, _sz, _vp, _vp]),
     ("plk_field_powers", _i, [_i, _vp, _sz, _vp]),
     ("plk_plonk_eval_polys_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp]),
