@@ -439,6 +439,28 @@ int plk_field_from_bytes(int field, const uint8_t* bytes, size_t count, uint64_t
 int plk_curve_point_to_bytes(int curve, const uint64_t* xy, const uint8_t* zero, size_t count, uint8_t* out_bytes);
 int plk_curve_point_from_bytes(int curve, const uint8_t* bytes, size_t count, uint64_t* out_xy, uint8_t* out_zero, uint8_t* status);
 
+/* ---- Pedersen generators: the BLAKE3 hash to the curve  (src/hash_to_curve.rs:13-76) ---------------------------------------- */
+/* blake_hash_usize_to_curve::<C>(seed_start + k), k < count (circuit_builder.rs:1127-1129, verifier.rs:151-174, plookup.rs:39-42):
+ * out_xy = count affine points x || y, 2L limbs each, Montgomery form; never the identity.  Try i of a seed hashes
+ * seed.to_canonical_u8_vec() || i || j with unkeyed BLAKE3 for j = 0, 1, ... until the first BYTES bytes of the output, the last
+ * shifted right by 8 BYTES - BITS, are below the modulus: that is x, and bit 0 of output byte BYTES is y_neg; the point is
+ * (x, y_neg ? -y : y) with y = Field::square_root(x^3 + B) for the first i at which the root exists.  i and j are u8 in the
+ * reference: a seed that needs a 257th value of either (probability below 2^-250) has no point there; here its coordinates are
+ * written as zero and the host-pointer forms return PLK_ERR_INVALID_ARG.  count == 0 is PLK_OK and launches nothing; count < 2^32.
+ * The _dev forms are asynchronous on `stream`, run on the calling thread's device and write device memory that feeds
+ * plk_msm_precompute_table_dev and the MSM contexts as it is (d_base_zero = NULL).  The output is bit-identical from run to run.
+ * These five entries take the COUNT first and the curve / field id second: the id-first entries form a pinned set, and these were
+ * added after it (as the Plookup entries were).
+ * PLK_H2C_NAIVE=1 (read once) runs one lane per seed through all its tries instead of rounds over a compacted work list: same bytes. */
+int plk_hash_to_curve(size_t count, int curve, uint64_t seed_start, uint64_t* out_xy);
+int plk_hash_to_curve_dev(size_t count, int curve, uint64_t seed_start, void* d_out_xy, void* stream);
+/* blake_hash_base_field_to_curve::<C>(seed_k): seeds are elements of the curve's base field, L limbs each, Montgomery form. */
+int plk_hash_field_to_curve(size_t count, int curve, const uint64_t* seeds, uint64_t* out_xy);
+int plk_hash_field_to_curve_dev(size_t count, int curve, const void* d_seeds, void* d_out_xy, void* stream);
+/* blake_field(iters[k], seeds[k]) alone, over any of the six fields: out_x (L limbs each, Montgomery form) and out_y_neg (0 / 1).
+ * The seam that separates a wrong hash from a wrong root.  Host pointers. */
+int plk_blake_field(size_t count, int field, const uint8_t* iters, const uint64_t* seeds, uint64_t* out_x, uint8_t* out_y_neg);
+
 /* r = log_inputs rounds of that fold at once, in the scaled form halo.hip keeps its generators in:
  *     out_i = g_i + sum_{t = 1 .. 2^r - 1} [s_t] g_{i + t n_out},   i < n_out,
  * g = 2^r n_out affine points (+ optional identity flags), the 2^r scalars in DEVICE memory (4 limbs each, Montgomery, scalar

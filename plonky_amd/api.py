@@ -756,3 +756,42 @@ def point_from_bytes(curve, b, with_status=False):
         raise ValueError(_lib.load().plk_last_error().decode())
     _lib.check(rc)
     return out, oz
+
+
+# ---- Pedersen generators: the BLAKE3 hash to the curve (hash_to_curve.rs:13-76) ----
+def _no_point(rc):
+    if rc == _lib.PLK_ERR_INVALID_ARG:
+        raise ValueError(_lib.load().plk_last_error().decode())
+    _lib.check(rc)
+
+
+def blake_field(field, iters, seeds):
+    """blake_field(iter, seed) per row: seeds (n, L) Montgomery limbs, iters a u8 per row (or one for all).  Returns (x (n, L), y_neg (n,))."""
+    a = _elems(field, seeds)
+    it = np.ascontiguousarray(np.broadcast_to(np.asarray(iters, dtype=np.uint8), (a.shape[0],)))
+    x = np.empty_like(a)
+    y_neg = np.zeros(a.shape[0], dtype=np.uint8)
+    _no_point(_lib.load().plk_blake_field(a.shape[0], field, _ptr(it), _ptr(a), _ptr(x), _ptr(y_neg)))
+    return x, y_neg
+
+
+def blake_hash_base_field_to_curve(curve, seeds):
+    """blake_hash_base_field_to_curve::<C>(seed) per row of seeds ((n, L) Montgomery limbs of the base field): (n, 2, L) affine points."""
+    a = _elems(CURVE_BASE_FIELD[curve], seeds)
+    out = np.empty((a.shape[0], 2, a.shape[1]), dtype=np.uint64)
+    _no_point(_lib.load().plk_hash_field_to_curve(a.shape[0], curve, _ptr(a), _ptr(out)))
+    return out
+
+
+def blake_hash_usize_to_curve(curve, seed, count=None):
+    """blake_hash_usize_to_curve::<C>(seed): (2, L); with count, the points of seed .. seed + count - 1: (count, 2, L)."""
+    n = 1 if count is None else int(count)
+    out = np.empty((n, 2, _CURVE_LIMBS[curve]), dtype=np.uint64)
+    _no_point(_lib.load().plk_hash_to_curve(n, curve, int(seed), _ptr(out)))
+    return out[0] if count is None else out
+
+
+def pedersen_generators(curve, degree):
+    """circuit_builder.rs:1127-1129: (g[0 .. degree), h = the point of seed degree, u = the point of seed degree + 1)."""
+    pts = blake_hash_usize_to_curve(curve, 0, degree + 2)
+    return pts[:degree], pts[degree], pts[degree + 1]

@@ -1458,6 +1458,72 @@ int plk_curve_point_from_bytes(int curve, const uint8_t* bytes, size_t count, ui
     return PLK_OK;
 }
 
+// ---- the BLAKE3 hash to the curve (hash_to_curve.hip): count first, id second (include/plonky_hip.h says why) ----
+int plk_hash_to_curve_dev(size_t count, int curve, uint64_t seed_start, void* d_out_xy, void* stream) {
+    PLK_API;
+    return hash_to_curve_dev_impl(curve, 0, nullptr, seed_start, count, d_out_xy, nullptr, as_stream(stream));
+}
+int plk_hash_field_to_curve_dev(size_t count, int curve, const void* d_seeds, void* d_out_xy, void* stream) {
+    PLK_API;
+    return hash_to_curve_dev_impl(curve, 1, d_seeds, 0, count, d_out_xy, nullptr, as_stream(stream));
+}
+// the host-pointer forms: seeds == nullptr is the integer form
+static int hash_to_curve_host(int curve, const uint64_t* seeds, int field_seeds, uint64_t seed_start, size_t count, uint64_t* out_xy) {
+    PLK_TRY(hash_to_curve_check(curve, count));
+    if (count == 0) return PLK_OK;
+    if (!out_xy || (field_seeds && !seeds)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t coord = (size_t)curve_limbs(curve) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(seeds, count * coord);
+    c.pin(out_xy, count * 2 * coord);
+    void *dseeds = nullptr, *dp = nullptr, *ds = nullptr;
+    if (field_seeds) PLK_TRY(c.in(dseeds, seeds, count * coord));
+    PLK_TRY(c.tmp(dp, count * 2 * coord));
+    PLK_TRY(c.tmp(ds, count));
+    PLK_TRY(hash_to_curve_dev_impl(curve, field_seeds, dseeds, seed_start, count, dp, ds, c.stream()));
+    std::vector<uint8_t> st(count);
+    PLK_TRY(c.out(st.data(), ds, count));
+    PLK_TRY(c.out(out_xy, dp, count * 2 * coord));
+    PLK_TRY(c.finish());
+    for (size_t k = 0; k < count; ++k)
+        if (st[k])
+            return set_error(PLK_ERR_INVALID_ARG, "seed %zu has no point: %s passed 255 (hash_to_curve.rs:%s)", k, st[k] == 1 ? "j" : "i", st[k] == 1 ? "48" : "74");
+    return PLK_OK;
+}
+int plk_hash_to_curve(size_t count, int curve, uint64_t seed_start, uint64_t* out_xy) {
+    PLK_API;
+    return hash_to_curve_host(curve, nullptr, 0, seed_start, count, out_xy);
+}
+int plk_hash_field_to_curve(size_t count, int curve, const uint64_t* seeds, uint64_t* out_xy) {
+    PLK_API;
+    return hash_to_curve_host(curve, seeds, 1, 0, count, out_xy);
+}
+int plk_blake_field(size_t count, int field, const uint8_t* iters, const uint64_t* seeds, uint64_t* out_x, uint8_t* out_y_neg) {
+    PLK_API;
+    PLK_TRY(blake_field_check(field, count));
+    if (count == 0) return PLK_OK;
+    if (!iters || !seeds || !out_x || !out_y_neg) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t elem = (size_t)field_limbs(field) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void *di = nullptr, *dseeds = nullptr, *dx = nullptr, *dy = nullptr, *ds = nullptr;
+    PLK_TRY(c.in(di, iters, count));
+    PLK_TRY(c.in(dseeds, seeds, count * elem));
+    PLK_TRY(c.tmp(dx, count * elem));
+    PLK_TRY(c.tmp(dy, count));
+    PLK_TRY(c.tmp(ds, count));
+    PLK_TRY(blake_field_dev_impl(field, di, dseeds, count, dx, dy, ds, c.stream()));
+    std::vector<uint8_t> st(count);
+    PLK_TRY(c.out(st.data(), ds, count));
+    PLK_TRY(c.out(out_x, dx, count * elem));
+    PLK_TRY(c.out(out_y_neg, dy, count));
+    PLK_TRY(c.finish());
+    for (size_t k = 0; k < count; ++k)
+        if (st[k]) return set_error(PLK_ERR_INVALID_ARG, "seed %zu has no x: j passed 255 (hash_to_curve.rs:48)", k);
+    return PLK_OK;
+}
+
 // ---- scalar side of an IPA round ----
 int plk_field_inner_product_dev(int field, const void* d_a, const void* d_b, size_t count, void* d_out, void* stream) {
     PLK_API;

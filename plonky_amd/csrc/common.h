@@ -172,6 +172,13 @@ int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, co
 int field_bytes_impl(int field, int from_bytes, const void* d_in, size_t count, void* d_out, unsigned* d_bad, hipStream_t stream);
 int point_bytes_impl(int curve, int from_bytes, const void* d_in, const void* d_zero, size_t count, void* d_out, void* d_out_zero, void* d_status,
                      hipStream_t stream);
+uint32_t curve_b(int curve);  // the curve constant B (A = 0 on every in-scope curve); serial.hip
+// the BLAKE3 hash to the curve (hash_to_curve.hip); the checks hold the refusals the host entries share
+int hash_to_curve_check(int curve, size_t count);
+int hash_to_curve_dev_impl(int curve, int field_seeds, const void* d_seeds, uint64_t seed_start, size_t count, void* d_out_xy, void* d_status,
+                           hipStream_t stream);
+int blake_field_check(int field, size_t count);
+int blake_field_dev_impl(int field, const void* d_iters, const void* d_seeds, size_t count, void* d_out_x, void* d_out_y_neg, void* d_status, hipStream_t stream);
 int field_batch_inverse_dev_impl(int field, const void* d_x, void* d_out, void* d_is_zero, unsigned* d_zero_count, size_t count, hipStream_t stream);
 int curve_batch_to_affine_dev_impl(int curve, size_t count, const void* d_xyz, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
 int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* d_constants, const void* d_wires, const void* d_s_sigma, const void* d_z,

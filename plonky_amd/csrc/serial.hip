@@ -9,6 +9,7 @@
 // stops after the mask byte of the identity; a record here simply leaves the rest unused).
 #include "common.h"
 #include "ec.cuh"
+#include "fe_sqrt.cuh"
 #include "fp.cuh"
 #include "tables.cuh"
 
@@ -51,67 +52,6 @@ template <class P> __global__ void k_field_from_bytes(const uint8_t* __restrict_
         return;
     }
     fe_store<P>(out + i * (P::NL / 4), fe_from_canonical<P>(c));
-}
-
-// x^e for a multi-limb exponent (little-endian 32-bit words)
-template <class P> PLK_DI Fe<P> fe_pow_limbs(const Fe<P>& x, const uint32_t (&e)[P::NL]) {
-    Fe<P> r = fe_one<P>();
-    bool started = false;
-    for (int i = P::NL - 1; i >= 0; --i)
-        for (int b = 31; b >= 0; --b) {
-            if (started) r = fe_sqr<P>(r);
-            if ((e[i] >> b) & 1u) {
-                r = started ? fe_mul<P>(r, x) : x;
-                started = true;
-            }
-        }
-    return r;
-}
-// Field::square_root (field.rs:440-472): Tonelli-Shanks with z = g^T, T = (p - 1) / 2^TWO_ADICITY.  Returns false for a
-// non-residue (the reference tests Euler's criterion first; here the same fact falls out of the loop: b = a^T has order
-// dividing 2^(adicity - 1) exactly when a is a square).
-template <class P> PLK_DNI bool fe_sqrt(const Fe<P>& a, Fe<P>& root) {
-    if (fe_is_zero<P>(a)) {
-        root = a;
-        return true;
-    }
-    // (T - 1) / 2 from the modulus: T = (p - 1) >> adicity is odd
-    uint32_t e[P::NL];
-    {
-        uint32_t t[P::NL];
-        for (int i = 0; i < P::NL; ++i) t[i] = P::MOD[i];
-        t[0] -= 1u;  // p is odd
-        constexpr int sh = P::TWO_ADICITY + 1;  // (T - 1) / 2 = (p - 1) >> (adicity + 1), T odd
-        for (int i = 0; i < P::NL; ++i) {
-            const int src = i + sh / 32, bit = sh % 32;
-            uint32_t lo = src < P::NL ? t[src] : 0u, hi = src + 1 < P::NL ? t[src + 1] : 0u;
-            e[i] = bit ? (lo >> bit) | (hi << (32 - bit)) : lo;
-        }
-    }
-    Fe<P> z = fe_const<P>(P::ROOT_2ADIC);
-    Fe<P> w = fe_pow_limbs<P>(a, e);
-    Fe<P> x = fe_mul<P>(w, a);
-    Fe<P> b = fe_mul<P>(x, w);
-    const Fe<P> one = fe_one<P>();
-    int v = P::TWO_ADICITY;
-    while (!fe_eq<P>(b, one)) {
-        int k = 0;
-        Fe<P> b2k = b;
-        while (!fe_eq<P>(b2k, one)) {
-            b2k = fe_sqr<P>(b2k);
-            ++k;
-            if (k >= v) return false;  // not a square
-        }
-        const int j = v - k - 1;
-        w = z;
-        for (int s = 0; s < j; ++s) w = fe_sqr<P>(w);
-        z = fe_sqr<P>(w);
-        b = fe_mul<P>(b, z);
-        x = fe_mul<P>(x, w);
-        v = k;
-    }
-    root = x;
-    return true;
 }
 
 // serialization.rs:33-45
@@ -176,7 +116,7 @@ int field_bytes_impl(int field, int from_bytes, const void* d_in, size_t count, 
 
 // curve constants B (A = 0): tweedledee_curve.rs:11-12 (5), tweedledum_curve.rs:11-13 (7), bls12_377_curve.rs:14-15 (1)
 // pallas_curve.rs:12, vesta_curve.rs:12 (5)
-static uint32_t curve_b(int curve) { return curve == PLK_CURVE_TWEEDLEDUM ? 7u : curve == PLK_CURVE_BLS12_377 ? 1u : 5u; }
+uint32_t curve_b(int curve) { return curve == PLK_CURVE_TWEEDLEDUM ? 7u : curve == PLK_CURVE_BLS12_377 ? 1u : 5u; }
 
 int point_bytes_impl(int curve, int from_bytes, const void* d_in, const void* d_zero, size_t count, void* d_out, void* d_out_zero, void* d_status,
                      hipStream_t stream) {

@@ -103,6 +103,24 @@ def gen_bases_dev(curve, n, g0_xy, d_xy, first=0, device="cuda"):
     return out
 
 
+def hash_to_curve_dev(curve, count, seed_start=0, seeds=None, out=None, device="cuda"):
+    """The Pedersen generators on the device (hash_to_curve.rs:53-76): the points of the integers seed_start .. seed_start + count - 1,
+    or, with seeds ((count, L) int64 CUDA tensor, Montgomery form), of those base-field elements.  (count, 2, L) int64 tensor that
+    msm_precompute_dev takes as it is."""
+    L = _CURVE_LIMBS[curve]
+    if seeds is not None:
+        assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.shape == (count, L)
+        device = seeds.device
+    if out is None:
+        out = torch.empty((count, 2, L), dtype=torch.int64, device=device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
+    if seeds is None:
+        _lib.check(_lib.load().plk_hash_to_curve_dev(count, curve, int(seed_start), ctypes.c_void_p(out.data_ptr()), _stream()))
+    else:
+        _lib.check(_lib.load().plk_hash_field_to_curve_dev(count, curve, ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
 def msm_precompute_dev(curve, bases, w=11, zero=None, device_window=0, table_free=False):
     """bases: (n, 2, L) int64 CUDA tensor.  table_free: no window tables (generators used once or a few times)."""
     assert bases.is_cuda and bases.dtype == torch.int64 and bases.is_contiguous()

@@ -107,6 +107,12 @@ SYMBOLS = [
     ("plk_field_from_bytes", _i, [_i, _vp, _sz, _vp]),
     ("plk_curve_point_to_bytes", _i, [_i, _vp, _vp, _sz, _vp]),
     ("plk_curve_point_from_bytes", _i, [_i, _vp, _sz, _vp, _vp, _vp]),
+    # the hash-to-curve entries take the count first (_sz) and the curve / field id second
+    ("plk_hash_to_curve", _i, [_sz, _i, _u64, _vp]),
+    ("plk_hash_to_curve_dev", _i, [_sz, _i, _u64, _vp, _vp]),
+    ("plk_hash_field_to_curve", _i, [_sz, _i, _vp, _vp]),
+    ("plk_hash_field_to_curve_dev", _i, [_sz, _i, _vp, _vp, _vp]),
+    ("plk_blake_field", _i, [_sz, _i, _vp, _vp, _vp, _vp]),
     ("plk_field_inner_product_dev", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("plk_field_fold_slices_dev", _i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("plk_halo_begin_dev", _i, [_i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp]),
