@@ -229,6 +229,37 @@ int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wire
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out);
 
+/* ---- the copy-constraint permutation  (src/partition.rs, src/plonk_util.rs) -------------------------------------------------------- */
+/* WirePartitions::to_sigma (partition.rs:108-136) and sigma_polynomials (plonk_util.rs:264-280): the step of CircuitBuilder::build
+ * (circuit_builder.rs:1107-1108, 1149) that turns the copy-constraint partitions into the six S_sigma columns.  n = 2^log_degree,
+ * log_degree <= 27.  Like the Plookup entries these two take the SIZE first and the field id second.  Fields: the 4-limb circuit scalar
+ * fields.  The union-find (TargetPartitions::merge, partition.rs:38-52) stays with the caller: the order of a partition's members is the
+ * order in which merge appended the lists, and the committed c_s_sigmas depend on it.
+ * The live wire partitions (those some wire's index still points to) arrive flattened: d_members, uint32[num_members], each a wire id
+ * input * n + gate (the reference's sigma indexing, partition.rs:132, over all NUM_WIRES = 9 inputs: ids are below 9n, a wire is routed
+ * iff its id is below 6n); d_offsets, uint32[num_partitions + 1], non-decreasing, offsets[0] = 0, offsets[num_partitions] = num_members.
+ * Empty partitions are allowed and skipped; non-routed wires may be listed or left out.  A decreasing d_offsets is outside the contract
+ * of the device form.  k_is[6]: host scalars as for plk_plonk_permutation_z_dev; g = primitive_root_of_unity(log_degree).
+ * d_sigma: uint32[6n], the return value of to_sigma: sigma[w] is the member after w in w's partition, the first after the last
+ * (get_neighbor, partition.rs:108-118).  d_s_sigma: [6][n] elements, the return value of sigma_polynomials:
+ * s_sigma[w] = k_is[sigma[w] / n] g^(sigma[w] % n), canonical Montgomery form - what plk_plonk_permutation_z_dev takes with sigma_stride 1
+ * and plk_ntt_dev with inverse = 1.  Either output may be null, not both.
+ * d_status (nullable, device, 3 x uint32, written in stream order): [0] = routed wires that are not listed exactly once, missing ones plus
+ * surplus listings (the reference's indices[&wire] panic, partition.rs:109); [1] = non-routed members in a partition of more than one
+ * member (the assert_valid panic, partition.rs:90-102); [2] = members that are not below 9n.  The outputs are unspecified when a word is
+ * nonzero; every id is compared with its bound before it indexes anything, whatever d_members holds.  Asynchronous on `stream`, the
+ * calling thread's device; working memory from the scratch pool; with d_s_sigma the first call for a (field, log_degree) builds the
+ * circuit-size tables that plk_plonk_permutation_z_dev shares.  An unknown field id, a null k_is and log_degree > 27 are
+ * PLK_ERR_INVALID_ARG before anything is launched. */
+int plk_plonk_sigma_dev(unsigned log_degree, int field, const void* d_members, const void* d_offsets, size_t num_partitions, size_t num_members,
+                        const uint64_t* k_is, void* d_sigma, void* d_s_sigma, void* d_status, void* stream);
+/* Same with host pointers (num_members = offsets[num_partitions]); sigma: 6n words, s_sigma: 6n elements, either may be null.  offsets is
+ * checked here (offsets[0] = 0, non-decreasing).  PLK_ERR_INVALID_ARG where the reference panics, with plk_last_error() starting
+ * "Non-routed wires should not be in a partition containing other wires" (status word [1]), "no entry found for key" (word [0]) or
+ * "wire id out of range" (word [2]). */
+int plk_plonk_sigma(unsigned log_degree, int field, const uint32_t* members, const uint32_t* offsets, size_t num_partitions, const uint64_t* k_is,
+                    uint32_t* sigma, uint64_t* s_sigma);
+
 /* ---- the Plookup prover  (plookup/src/plookup.rs) ------------------------------------------------------------------------------- */
 /* The sort and the two O(n) loops of `prove` that no other entry point covers.  N = 2^log_size = n + 1 is the order of the subgroup H.  These six
  * entries take the SIZE first and the field id second: the id-first entries form a pinned set, and these were added after it.  Fields:

@@ -545,6 +545,124 @@ def permutation_polynomial(field, degree, wire_values, s_sigma_values, k_is, bet
     return out
 
 
+# ---- the copy-constraint partitions and sigma (src/partition.rs, plonk_util.rs:264-280) ----
+class TargetPartitions:
+    """TargetPartitions (partition.rs:6-82), a host mirror.  Targets are hashable tuples: ("wire", gate, input) for Target::Wire and
+    ("virtual", index) for every other target (to_wire_partitions drops them).  The union-find stays on the host: the order of a
+    partition's members is the order in which merge appended the lists, and sigma - hence c_s_sigmas - depends on it."""
+
+    def __init__(self):
+        self.partitions = []
+        self.indices = {}
+
+    def get_partition(self, target):
+        return self.partitions[self.indices[target]]
+
+    def add_partition(self, target):  # partition.rs:30-34
+        self.indices[target] = len(self.partitions)
+        self.partitions.append([target])
+
+    def merge(self, a, b):
+        """partition.rs:38-52: a's list is appended to b's and a's members are re-pointed; a's old list stays where it is (the Rust
+        clones it), so a merged-away index keeps a stale list that no target points to."""
+        a_index, b_index = self.indices[a], self.indices[b]
+        if a_index != b_index:
+            a_partition = list(self.partitions[a_index])
+            for sibling in a_partition:
+                self.indices[sibling] = b_index
+            self.partitions[b_index].extend(a_partition)
+
+    def to_wire_partitions(self):  # partition.rs:54-81
+        partitions = [[(t[1], t[2]) for t in old if t[0] == "wire"] for old in self.partitions]
+        indices = {(t[1], t[2]): index for t, index in self.indices.items() if t[0] == "wire"}
+        result = WirePartitions(partitions, indices)
+        result.assert_valid()
+        return result
+
+
+class WirePartitions:
+    """WirePartitions (partition.rs:84-137): wires are (gate, input) pairs."""
+
+    def __init__(self, partitions, indices):
+        self.partitions = partitions
+        self.indices = indices
+
+    def assert_valid(self):  # partition.rs:90-102
+        for partition in self.partitions:
+            for _, inp in partition:
+                if inp >= NUM_ROUTED_WIRES:
+                    assert len(partition) == 1, "Non-routed wires should not be in a partition containing other wires"
+
+    def get_neighbor(self, wire):  # partition.rs:108-118
+        partition = self.partitions[self.indices[wire]]
+        n = len(partition)
+        for i in range(n):
+            if partition[i] == wire:
+                return partition[(i + 1) % n]
+        raise AssertionError("Wire not found in the expected partition")
+
+    def to_sigma(self):
+        """partition.rs:122-136, the reference's own loop (a linear scan per wire): for small sizes and tests; the device form is
+        to_csr + wire_partitions_to_sigma / device.sigma_dev."""
+        assert len(self.indices) % NUM_WIRES == 0
+        num_gates = len(self.indices) // NUM_WIRES
+        sigma = []
+        for inp in range(NUM_ROUTED_WIRES):
+            for gate in range(num_gates):
+                g, i = self.get_neighbor((gate, inp))
+                sigma.append(i * num_gates + g)
+        return sigma
+
+    def to_csr(self, degree):
+        """The flattened form plk_plonk_sigma[_dev] takes: (members, offsets) uint32 arrays over the LIVE partitions - those some wire's
+        index still points to, in the order of their indices; the stale lists merge leaves behind are dropped.  A member is the
+        wire id input * degree + gate."""
+        live = sorted(set(self.indices.values()))
+        offsets = np.zeros(len(live) + 1, dtype=np.uint32)
+        members = []
+        for k, q in enumerate(live):
+            members.extend(inp * degree + gate for gate, inp in self.partitions[q])
+            offsets[k + 1] = len(members)
+        return np.array(members, dtype=np.uint32), offsets
+
+
+def _sigma_panic(rc):
+    """the reference's panics behind PLK_ERR_INVALID_ARG of plk_plonk_sigma -> AssertionError with the library's text"""
+    if rc == _lib.PLK_ERR_INVALID_ARG:
+        msg = _lib.load().plk_last_error().decode("utf-8", "replace")
+        if msg.startswith(("Non-routed wires", "no entry found for key", "wire id out of range")):
+            raise AssertionError(msg)
+    _lib.check(rc)
+
+
+def wire_partitions_to_sigma(field, degree, members, offsets, k_is, want_values=True):
+    """to_sigma + sigma_polynomials through the device (plk_plonk_sigma; host arrays, copied through PCIe): members / offsets as
+    WirePartitions.to_csr gives them, k_is (6, 4) -> (sigma (6 degree,) uint32, s_sigma (6, degree, 4)).  Where the reference panics
+    (a routed wire that is not listed exactly once, a non-routed wire in company) -> AssertionError."""
+    log_degree = log2_strict(degree)
+    m = np.ascontiguousarray(members, dtype=np.uint32).reshape(-1)
+    o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    assert o.shape[0] >= 1, "offsets holds num_partitions + 1 entries"
+    assert int(o[-1]) == m.shape[0], "offsets[num_partitions] must be the number of members"
+    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, 4)
+    sigma = np.empty(NUM_ROUTED_WIRES * degree, dtype=np.uint32)
+    values = np.empty((NUM_ROUTED_WIRES, degree, 4), dtype=np.uint64) if want_values else None
+    _sigma_panic(_lib.load().plk_plonk_sigma(log_degree, field, _ptr(m), _ptr(o), o.shape[0] - 1, _ptr(ks), _ptr(sigma),
+                                             _ptr(values) if want_values else None))
+    return (sigma, values) if want_values else sigma
+
+
+def sigma_polynomials(field, sigma, degree, k_is):
+    """sigma_polynomials (plonk_util.rs:264-280): sigma, 6 degree entries below 6 degree -> (6, degree, 4), element (j, r) =
+    k_is[x / degree] g^(x % degree) for x = sigma[j degree + r].  The values of the identity permutation come from the device
+    (plk_plonk_sigma over singletons); sigma then picks among them."""
+    sg = np.ascontiguousarray(sigma, dtype=np.int64).reshape(-1)
+    n6 = NUM_ROUTED_WIRES * degree
+    assert sg.shape[0] == n6 and (sg.size == 0 or (0 <= sg.min() and sg.max() < n6)), "sigma maps [6n] to [6n]"
+    _, ident = wire_partitions_to_sigma(field, degree, np.arange(n6, dtype=np.uint32), np.arange(n6 + 1, dtype=np.uint32), k_is)
+    return np.ascontiguousarray(ident.reshape(n6, 4)[sg].reshape(NUM_ROUTED_WIRES, degree, 4))
+
+
 # ---- the Plookup prover's two loops (plookup/src/plookup.rs) ----
 def plookup_sorted_multiset(f, t):
     """`s` of the Plookup protocol: f ++ t sorted by t, as sort_by orders it (plookup.rs:171-177, a stable sort on the position of

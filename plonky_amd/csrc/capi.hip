@@ -897,6 +897,49 @@ int plk_plookup_sorted_multiset(unsigned log_size, int field, const uint64_t* f,
     PLK_TRY(c.out(s, ds, 2 * row - 32));
     return c.finish();
 }
+// ---- the copy-constraint permutation (sigma.hip): the size comes first, the field id second ----
+int plk_plonk_sigma_dev(unsigned log_degree, int field, const void* d_members, const void* d_offsets, size_t num_partitions, size_t num_members, const uint64_t* k_is,
+                        void* d_sigma, void* d_s_sigma, void* d_status, void* stream) {
+    PLK_API;
+    return plonk_sigma_dev_impl(log_degree, field, d_members, d_offsets, num_partitions, num_members, k_is, d_sigma, d_s_sigma, d_status, as_stream(stream));
+}
+int plk_plonk_sigma(unsigned log_degree, int field, const uint32_t* members, const uint32_t* offsets, size_t num_partitions, const uint64_t* k_is, uint32_t* sigma,
+                    uint64_t* s_sigma) {
+    PLK_API;
+    PLK_TRY(plonk_sigma_check(log_degree, field, num_partitions, 0, k_is));
+    if (!offsets) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    if (!sigma && !s_sigma) return set_error(PLK_ERR_INVALID_ARG, "neither sigma nor s_sigma is given");
+    // what the device form cannot see in time: the lanes' bisection needs offsets to start at 0 and never to decrease
+    if (offsets[0] != 0) return set_error(PLK_ERR_INVALID_ARG, "offsets[0] is %u, not 0", offsets[0]);
+    for (size_t q = 0; q < num_partitions; ++q)
+        if (offsets[q + 1] < offsets[q]) return set_error(PLK_ERR_INVALID_ARG, "offsets decrease at partition %zu (%u after %u)", q, offsets[q + 1], offsets[q]);
+    const size_t num_members = offsets[num_partitions];
+    PLK_TRY(plonk_sigma_check(log_degree, field, num_partitions, num_members, k_is));
+    if (num_members && !members) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t n6 = (size_t)6 << log_degree;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void *dm = nullptr, *dof = nullptr, *dsig = nullptr, *dval = nullptr, *dst = nullptr;
+    PLK_TRY(c.in(dm, members, num_members * 4));
+    PLK_TRY(c.in(dof, offsets, (num_partitions + 1) * 4));
+    PLK_TRY(c.tmp(dsig, n6 * 4));
+    if (s_sigma) PLK_TRY(c.tmp(dval, n6 * 32));
+    PLK_TRY(c.tmp(dst, 3 * sizeof(uint32_t)));
+    PLK_TRY(plonk_sigma_dev_impl(log_degree, field, dm, dof, num_partitions, num_members, k_is, dsig, dval, dst, c.stream()));
+    uint32_t st[3] = {0, 0, 0};
+    PLK_TRY(c.out(st, dst, sizeof(st)));
+    PLK_TRY(c.sync());
+    if (st[0] || st[1] || st[2]) {
+        c.done = true;
+        if (st[2]) return set_error(PLK_ERR_INVALID_ARG, "wire id out of range: %u members are not below 9 n", st[2]);
+        if (st[1])
+            return set_error(PLK_ERR_INVALID_ARG, "Non-routed wires should not be in a partition containing other wires: %u of them are (partition.rs:94-98)", st[1]);
+        return set_error(PLK_ERR_INVALID_ARG, "no entry found for key: %u routed wires are not listed exactly once (partition.rs:109)", st[0]);
+    }
+    if (sigma) PLK_TRY(c.out(sigma, dsig, n6 * 4));
+    if (s_sigma) PLK_TRY(c.out(s_sigma, dval, n6 * 32));
+    return c.finish();
+}
 int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* constants, const uint64_t* local_wires, const uint64_t* right_wires,
                                        const uint64_t* below_wires, const uint64_t* inner_zeta, const uint64_t* inner_a, uint64_t* out) {
     PLK_API;

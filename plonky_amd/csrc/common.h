@@ -186,6 +186,12 @@ int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* 
                                     const uint64_t* inner_a, void* d_out, hipStream_t stream);
 int plonk_permutation_z_dev_impl(int field, unsigned log_degree, const void* d_wires, const void* d_s_sigma, unsigned sigma_stride, const uint64_t* k_is,
                                  const uint64_t* beta, const uint64_t* gamma, void* d_out, void* d_status, hipStream_t stream);
+// the copy-constraint permutation (sigma.hip): size first, then the field id; the check holds the refusals the host entry shares
+int plonk_sigma_check(unsigned log_degree, int field, size_t num_partitions, size_t num_members, const uint64_t* k_is);
+int plonk_sigma_dev_impl(unsigned log_degree, int field, const void* d_members, const void* d_offsets, size_t num_partitions, size_t num_members, const uint64_t* k_is,
+                         void* d_sigma, void* d_s_sigma, void* d_status, hipStream_t stream);
+// the cached R-form powers of the 8n-th root (plonk.hip: PlonkTables::xs_lo / xs_hi); PLK_NO_MATCH for a field outside the 4-limb ones
+int plonk_domain_powers(int field, unsigned log_degree, hipStream_t stream, const void** xs_lo, const void** xs_hi, std::shared_ptr<const void>* hold);
 // the Plookup prover's two loops (plookup.hip): size first, then the field id (include/plonky_hip.h says why)
 int plookup_grand_product_dev_impl(unsigned log_size, int field, const void* d_f, const void* d_t, const void* d_s, const uint64_t* beta, const uint64_t* gamma,
                                    void* d_out, void* d_status, hipStream_t stream);

@@ -130,6 +130,18 @@ template <class P> static int get_plonk_tables(int log_degree, hipStream_t strea
     return PLK_OK;
 }
 
+// the R-form powers of the 8n-th root for sigma.hip: g_n^r = plonk_x(xs_lo, xs_hi, 8 r); *hold shares ownership of the tables
+int plonk_domain_powers(int field, unsigned log_degree, hipStream_t stream, const void** xs_lo, const void** xs_hi, std::shared_ptr<const void>* hold) {
+    return with_field4(field, [&](auto tag) {
+        std::shared_ptr<PlonkTables> t;
+        PLK_TRY(get_plonk_tables<tag_t<decltype(tag)>>((int)log_degree, stream, t));
+        *xs_lo = t->xs_lo;
+        *xs_hi = t->xs_hi;
+        *hold = t;
+        return (int)PLK_OK;
+    });
+}
+
 // ---------------------------------------------------------------------------------------------
 // evaluate_all_constraints (gates/mod.rs:46-125): the unified constraint set at one point
 // ---------------------------------------------------------------------------------------------

@@ -230,6 +230,72 @@ def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k
     return (out, status) if want_status else out
 
 
+# ---- the copy-constraint permutation and the setup-time half of CircuitBuilder::build ----
+def sigma_dev(field, log_degree, members, offsets, k_is, want_sigma=True, status=False):
+    """to_sigma (partition.rs:108-136) + sigma_polynomials (plonk_util.rs:264-280) on device-resident partitions: int32 CUDA tensors
+    members (M,) (wire ids input * n + gate) and offsets (P + 1,), as api.WirePartitions.to_csr gives them; k_is (6, 4) host limbs.
+    Returns (sigma (6 n,) int32 or None, s_sigma (6, n, 4) int64) - s_sigma is what permutation_polynomial_dev takes with
+    sigma_stride=1 and ntt_dev with inverse=True; with status=True (or a (3,) int32 CUDA tensor) also the status words, written in
+    stream order: [0] routed wires not listed exactly once, [1] non-routed members in a partition of more than one, [2] ids >= 9 n
+    (the outputs are unspecified when one is nonzero)."""
+    n = 1 << log_degree
+    for t in (members, offsets):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1
+    assert offsets.numel() >= 1
+    sigma = torch.empty(6 * n, dtype=torch.int32, device=members.device) if want_sigma else None
+    values = torch.empty((6, n, 4), dtype=torch.int64, device=members.device)
+    want_status = status is not None and status is not False
+    if status is True:
+        status = torch.empty(3, dtype=torch.int32, device=members.device)
+    if want_status:
+        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 3
+    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(6, 4)
+    _lib.check(_lib.load().plk_plonk_sigma_dev(log_degree, field, ctypes.c_void_p(members.data_ptr() if members.numel() else None),
+                                               ctypes.c_void_p(offsets.data_ptr()), offsets.numel() - 1, members.numel(), ks.ctypes.data_as(ctypes.c_void_p),
+                                               ctypes.c_void_p(sigma.data_ptr() if want_sigma else None), ctypes.c_void_p(values.data_ptr()),
+                                               ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
+    return (sigma, values, status) if want_status else (sigma, values)
+
+
+class CircuitKey:
+    """What circuit_key_dev returns: the setup-time fields of Circuit (circuit_builder.rs:1162-1190) that are computed, all on the device."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def circuit_key_dev(curve, log_degree, gate_constants, members, offsets, k_is, w=11):
+    """The setup-time half of CircuitBuilder::build (circuit_builder.rs:1118-1160) chained on the device.  gate_constants: (n, 6, 4)
+    int64 CUDA tensor, indexed by gate first as the builder holds it; members / offsets / k_is as for sigma_dev, over the curve's
+    scalar field.  Returns a CircuitKey with
+      pedersen_g (n, 2, L), pedersen_h (2, L), u (2, L)     blake_hash_usize_to_curve of 0..n-1, n, n + 1 (hash_to_curve_dev)
+      msm_precomputation                                    over pedersen_g ++ [pedersen_h], the form api.commitment_precompute builds
+      constant_polynomials (6, n, 4), constants_8n (6, 8n, 4), c_constants ((6, 2, L), (6,) zero flags)
+      sigma (6n,), s_sigma_polynomials (6, n, 4), s_sigma_values_8n (6, 8n, 4), c_s_sigmas ((6, 2, L), (6,))
+    The commitments are unblinded (plonk_util.rs:215-231 with blinding off): the scalar of pedersen_h is zero."""
+    from .api import CURVE_SCALAR_FIELD
+    field = CURVE_SCALAR_FIELD[curve]
+    n = 1 << log_degree
+    assert gate_constants.is_cuda and gate_constants.dtype == torch.int64 and tuple(gate_constants.shape) == (n, 6, 4)
+    gens = hash_to_curve_dev(curve, n + 2, device=gate_constants.device)
+    pre = msm_precompute_dev(curve, gens[: n + 1], w=w)
+
+    def commit(polys):
+        return msm_execute_dev(pre, torch.cat([polys, torch.zeros((polys.shape[0], 1, 4), dtype=torch.int64, device=polys.device)], dim=1).contiguous())
+
+    wire_constants = gate_constants.permute(1, 0, 2).contiguous()  # transpose (circuit_builder.rs:1136)
+    constant_polynomials = ntt_dev(field, wire_constants, inverse=True)
+    constants_8n = ntt_padded_dev(field, constant_polynomials, log_degree + 3)
+    c_constants = commit(constant_polynomials)
+    sigma, sigma_chunks = sigma_dev(field, log_degree, members, offsets, k_is)
+    s_sigma_polynomials = ntt_dev(field, sigma_chunks, inverse=True)
+    s_sigma_values_8n = ntt_padded_dev(field, s_sigma_polynomials, log_degree + 3)
+    c_s_sigmas = commit(s_sigma_polynomials)
+    return CircuitKey(pedersen_g=gens[:n], pedersen_h=gens[n], u=gens[n + 1], msm_precomputation=pre, constant_polynomials=constant_polynomials,
+                      constants_8n=constants_8n, c_constants=c_constants, sigma=sigma, s_sigma_polynomials=s_sigma_polynomials,
+                      s_sigma_values_8n=s_sigma_values_8n, c_s_sigmas=c_s_sigmas)
+
+
 # ---- the Plookup prover's two loops on device-resident tables (plookup/src/plookup.rs) ----
 def plookup_grand_polynomial_dev(field, log_size, f, t, s, beta, gamma, out=None, status=False):
     """grand_polynomial (plookup.rs:180-202): int64 CUDA tensors f (N, 4) (f_padded; the last row is not read), t (N, 4),

@@ -64,6 +64,9 @@ SYMBOLS = [
     ("plk_plookup_vanishing_points", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plookup_sorted_multiset_dev", _i, [_u, _i, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plookup_sorted_multiset", _i, [_u, _i, _vp, _vp, _vp, _vp]),
+    # the sigma entries take the size first (_u) and the field id second, like the Plookup entries
+    ("plk_plonk_sigma_dev", _i, [_u, _i, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_plonk_sigma", _i, [_u, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("plk_field_powers_dev", _i, [_i, _vp, _sz, _vp, _vp]),
     ("plk_field_powers", _i, [_i, _vp, _sz, _vp]),
     ("plk_plonk_eval_polys_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp]),
