@@ -599,6 +599,23 @@ int plk_msm_get_timings(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
  * Montgomery reduction at the edge of their column bound; the column accumulators of the quotient numerator) - parity tests only.
  * b ignored for unary. */
 int plk_field_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
+/* Element-wise point arithmetic of the MSM kernels (ecz.cuh, ecz_coop.cuh) on host arrays of `count` <= 2048 elements - parity tests only
+ * (tests/test_gpu_group_law.py compares every result with big integers).  An operand is an affine point (2L limbs, Montgomery; identity
+ * flag, array nullable) and a NON-ZERO field element lambda (L limbs, Montgomery): the kernel forms the XYZZ representative
+ * (x l^2, y l^3, l^2, l^3) on the working limbs.  flags[i] bit 0 "inflate": 6p is added to X and 2p to Y of every XYZZ operand of
+ * element i, carried limbs - the upper end of the accumulator invariant (X < 8p, Y < 4p); bit 1: the negate argument of op 5.
+ *   op 0 xyzzz_add(A, B)   1 xyzzz_dbl(A)   2 xyzzz_add_q(A, B)   3 xyzzz_dbl_q(A)          (0, 1: one lane, 2, 3: one quad per element)
+ *   op 4 xyzzz_madd(A, affine B), 5 xyzzz_madd_entry(A, affine B, negate) + xyzzz_settle: b_lambda is not read; an identity B
+ *        leaves A as it is (the accumulation never meets one)
+ *   op 6 xyzzz_dbl_q applied `param` times, 1 <= param <= 24
+ *   op 7 wave_sum_q over groups of `param` (1, 2, 4, 8, 16) adjacent quads: result g = sum of elements g param .. g param + param - 1
+ *        (a short last group is filled with identities): ceil(count / param) results
+ *   op 8 xyzzz_dbl_q(xyzzz_add_q(xyzzz_add_q(A, B), A)) = 2 (2A + B): results of the quad law fed back into it
+ * Every result leaves as the unique affine point: out_xy 2L limbs, out_zero one byte per result.  *mismatch: lanes of a quad (op 7: of a
+ * group) whose affine result differs from the first lane's - 0 on a healthy build.  An unknown curve id, op, count or param is
+ * PLK_ERR_INVALID_ARG before anything is launched. */
+int plk_curve_op(int curve, int op, unsigned param, size_t count, const uint64_t* a_xy, const uint8_t* a_zero, const uint64_t* a_lambda, const uint64_t* b_xy,
+                 const uint8_t* b_zero, const uint64_t* b_lambda, const uint8_t* flags, uint64_t* out_xy, uint8_t* out_zero, unsigned* mismatch);
 /* The integer-ALU ceilings of the GPU the calling thread runs on, measured now (~60 ms; G operations per second over the whole GPU):
  * out[0] v_mad_u64_u32 lane-operations (8 waves per SIMD, 8 independent chains per lane) - the raw issue rate of the instruction a
  * modular multiplication is made of (126 per 9-limb product, 294 per 14-limb product): the hardware-referenced roofline of every

@@ -470,6 +470,30 @@ def field_op(field, op, a, b=None):
     return out
 
 
+CURVE_OPS = {"add": 0, "dbl": 1, "add_q": 2, "dbl_q": 3, "madd": 4, "madd_entry": 5, "dbl_q_times": 6, "wave_sum_q": 7, "chain_q": 8}
+CURVE_OP_INFLATE, CURVE_OP_NEGATE = 1, 2
+
+
+def curve_op(curve, op, a, b=None, flags=None, param=0):
+    """Element-wise device point arithmetic (plk_curve_op: parity tests of ecz.cuh / ecz_coop.cuh).  a, b: (points (n, 2, L), identity
+    flags (n,) or None, lambdas (n, L)).  Returns (affine results (m, 2, L), zero flags (m,), mismatch word); m = ceil(n / param) for
+    "wave_sum_q", n otherwise."""
+    L = _CURVE_LIMBS[curve]
+    u64 = lambda x, *shape: np.ascontiguousarray(x, dtype=np.uint64).reshape(*shape)
+    u8 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
+    axy, az, al = u64(a[0], -1, 2, L), u8(a[1]), u64(a[2], -1, L)
+    n = axy.shape[0]
+    bxy, bz, bl = (None, None, None) if b is None else (u64(b[0], n, 2, L), u8(b[1]), None if b[2] is None else u64(b[2], n, L))
+    fl = np.zeros(n, dtype=np.uint8) if flags is None else u8(flags)
+    code = CURVE_OPS[op]
+    m = -(-n // param) if code == 7 else n
+    out, oz, mism = np.zeros((m, 2, L), dtype=np.uint64), np.zeros(m, dtype=np.uint8), ctypes.c_uint(0xFFFFFFFF)
+    ptr = lambda x: None if x is None else _ptr(x)
+    _lib.check(_lib.load().plk_curve_op(curve, code, param, n, ptr(axy), ptr(az), ptr(al), ptr(bxy), ptr(bz), ptr(bl), ptr(fl), ptr(out), ptr(oz),
+                                        ctypes.byref(mism)))
+    return out, oz, int(mism.value)
+
+
 def msm_debug_digits(curve, scalars, window_bits):
     """The MSM's digit recoding on its own (to_digits, curve_msm.rs:159-180): scalars (n, 4) Montgomery limbs in the curve's scalar field
     -> (n, ceil((BITS + 1) / w)) signed digits as the ordering kernels form them, and the reference's unsigned digits rebuilt from them

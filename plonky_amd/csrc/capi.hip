@@ -57,6 +57,8 @@ int msm_table_digits(int curve, unsigned w);
 int msm_reference_table_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned w, void* d_out_xy, void* d_out_zero,
                                  hipStream_t stream);
 int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t quads, uint32_t* counts);
+int curve_op_dev_impl(int curve, int op, unsigned param, uint32_t count, const void* d_a_xy, const void* d_a_zero, const void* d_a_lambda, const void* d_b_xy,
+                      const void* d_b_zero, const void* d_b_lambda, const void* d_flags, void* d_out_xy, void* d_out_zero, void* d_mismatch);
 int msm_set_profiling_impl(plk_msm_ctx* ctx, int enable);
 int msm_get_timings_impl(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
 int ntt_set_profiling_impl(int enable);
@@ -1709,6 +1711,46 @@ int plk_bench_ceilings(double* out, unsigned n_out) { PLK_API; return bench_ceil
 int plk_field_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
     PLK_API;
     return field_op_impl(field, op, a, b, out, count);
+}
+
+int plk_curve_op(int curve, int op, unsigned param, size_t count, const uint64_t* a_xy, const uint8_t* a_zero, const uint64_t* a_lambda, const uint64_t* b_xy,
+                 const uint8_t* b_zero, const uint64_t* b_lambda, const uint8_t* flags, uint64_t* out_xy, uint8_t* out_zero, unsigned* mismatch) {
+    PLK_API;
+    const int L = curve_limbs(curve);
+    if (L < 0) return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
+    if (op < 0 || op > 8) return set_error(PLK_ERR_INVALID_ARG, "bad curve op %d", op);
+    if (count > 2048) return set_error(PLK_ERR_INVALID_ARG, "%zu elements (at most 2048 per call)", count);
+    if (op == 6 && (param < 1 || param > 24)) return set_error(PLK_ERR_INVALID_ARG, "%u doublings (1..24)", param);
+    if (op == 7 && !(param == 1 || param == 2 || param == 4 || param == 8 || param == 16)) return set_error(PLK_ERR_INVALID_ARG, "groups of %u quads (1, 2, 4, 8, 16)", param);
+    if (!mismatch) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    *mismatch = 0;
+    if (count == 0) return PLK_OK;
+    const bool has_b = op == 0 || op == 2 || op == 4 || op == 5 || op == 8, b_affine = op == 4 || op == 5;
+    if (!a_xy || !a_lambda || !flags || !out_xy || !out_zero || (has_b && (!b_xy || (!b_affine && !b_lambda)))) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    PLK_TRY(ensure_device());
+    const size_t results = op == 7 ? (count + param - 1) / param : count, pt = (size_t)2 * L * 8;
+    DevBuf da, daz, dal, db, dbz, dbl, df, dout, doz, dm;
+    auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int {
+        PLK_TRY(d.alloc(bytes));
+        PLK_HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        return PLK_OK;
+    };
+    PLK_TRY(up(da, a_xy, count * pt));
+    PLK_TRY(up(dal, a_lambda, count * pt / 2));
+    PLK_TRY(up(df, flags, count));
+    if (a_zero) PLK_TRY(up(daz, a_zero, count));
+    if (has_b) PLK_TRY(up(db, b_xy, count * pt));
+    if (has_b && !b_affine) PLK_TRY(up(dbl, b_lambda, count * pt / 2));
+    if (has_b && b_zero) PLK_TRY(up(dbz, b_zero, count));
+    PLK_TRY(dout.alloc(results * pt));
+    PLK_TRY(doz.alloc(results));
+    PLK_TRY(dm.alloc(4));
+    PLK_HIP_TRY(hipMemset(dm.p, 0, 4));
+    PLK_TRY(curve_op_dev_impl(curve, op, param, (uint32_t)count, da.p, daz.p, dal.p, db.p, dbz.p, dbl.p, df.p, dout.p, doz.p, dm.p));
+    PLK_HIP_TRY(hipMemcpy(out_xy, dout.p, results * pt, hipMemcpyDeviceToHost));
+    PLK_HIP_TRY(hipMemcpy(out_zero, doz.p, results, hipMemcpyDeviceToHost));
+    PLK_HIP_TRY(hipMemcpy(mismatch, dm.p, 4, hipMemcpyDeviceToHost));
+    return PLK_OK;
 }
 
 int plk_curve_gen_bases_dev(int curve, size_t n, uint64_t first, const uint64_t* g0_xy, const uint64_t* d_xy, void* d_out_xy, void* stream) {

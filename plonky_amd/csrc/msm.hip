@@ -370,6 +370,127 @@ __global__ void __launch_bounds__(256) k_selftest_quad(const uint4* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// plk_curve_op: one point operation of ecz.cuh / ecz_coop.cuh per element, on operands the caller chooses, result in affine form.
+// The parity tests compare it with big integers (tests/test_gpu_group_law.py): unlike the self-test above nothing here compares
+// one law of this library with another.
+// ---------------------------------------------------------------------------------------------
+constexpr int CURVE_OP_ADD = 0, CURVE_OP_DBL = 1, CURVE_OP_ADD_Q = 2, CURVE_OP_DBL_Q = 3, CURVE_OP_MADD = 4, CURVE_OP_MADD_ENTRY = 5,
+              CURVE_OP_DBL_Q_TIMES = 6, CURVE_OP_WAVE_SUM_Q = 7, CURVE_OP_CHAIN_Q = 8, CURVE_OP_COUNT = 9;
+constexpr uint8_t CURVE_OP_INFLATE = 1, CURVE_OP_NEGATE = 2;
+constexpr bool curve_op_is_quad(int op) { return op == CURVE_OP_ADD_Q || op == CURVE_OP_DBL_Q || op >= CURVE_OP_DBL_Q_TIMES; }
+
+struct CurveOpArgs {
+    const uint4 *a_xy, *a_lam, *b_xy, *b_lam;   // affine points (2L limbs) and lambda (L limbs), Montgomery form
+    const uint8_t *a_zero, *b_zero;             // identity flags, nullable
+    const uint8_t* flags;
+    uint4* out_xy;
+    uint8_t* out_zero;
+    uint32_t* mismatch;
+    uint32_t count, param;
+    int op;
+};
+
+// R-form words of the interface -> R'-form working limbs, value < 2p, exactly normalised
+template <class FP> PLK_DI Fz<FP> curve_op_load(const uint4* src) { return fz_mul<FP>(fz_from_fe<FP>(fe_load<FP>(src)), fz_const_r_to_rprime<FP>()); }
+// the representative (x l^2, y l^3, l^2, l^3) of the affine point e; inflated: X + 6p, Y + 2p with carried limbs (X < 8p, Y < 4p)
+template <class FP> PLK_DI XyzzZ<FP> curve_op_operand(const uint4* xy, const uint8_t* zero, const uint4* lam, uint32_t e, bool inflate) {
+    constexpr int W = FP::NL / 4;
+    if (zero && zero[e]) return xyzzz_identity<FP>();
+    const Fz<FP> l = curve_op_load<FP>(lam + (size_t)e * W);
+    XyzzZ<FP> r;
+    r.zz = fz_sqr<FP>(l);
+    r.zzz = fz_mul<FP>(r.zz, l);
+    r.x = fz_mul<FP>(curve_op_load<FP>(xy + (size_t)e * 2 * W), r.zz);
+    r.y = fz_mul<FP>(curve_op_load<FP>(xy + (size_t)e * 2 * W + W), r.zzz);
+    r.inf = false;
+    if (inflate) {
+        const Fz<FP> z = fz_zero<FP>();
+        r.x = fz_sub<FP, 2>(fz_sub<FP, 1>(r.x, z), z);  // + 2p + 4p
+        r.y = fz_sub<FP, 1>(r.y, z);                    // + 2p
+    }
+    return r;
+}
+
+// ops 0, 1, 4, 5: one lane per element
+template <class C>
+__global__ void __launch_bounds__(256) k_curve_op_lane(CurveOpArgs g) {
+    using FP = typename C::FP;
+    constexpr int W = FP::NL / 4;
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= g.count) return;
+    const uint8_t fl = g.flags[e];
+    XyzzZ<FP> a = curve_op_operand<FP>(g.a_xy, g.a_zero, g.a_lam, e, fl & CURVE_OP_INFLATE);
+    const bool b_ident = g.b_zero && g.b_zero[e];
+    switch (g.op) {
+        case CURVE_OP_ADD: a = xyzzz_add<FP>(a, curve_op_operand<FP>(g.b_xy, g.b_zero, g.b_lam, e, fl & CURVE_OP_INFLATE)); break;
+        case CURVE_OP_DBL: a = xyzzz_dbl<FP>(a); break;
+        case CURVE_OP_MADD:
+            if (!b_ident) {  // a table entry is never the identity: the accumulation has no branch for it
+                const Fz<FP> x2 = fz_from_fe<FP>(fz_to_fe_canonical<FP>(curve_op_load<FP>(g.b_xy + (size_t)e * 2 * W)));
+                const Fz<FP> y2 = fz_from_fe<FP>(fz_to_fe_canonical<FP>(curve_op_load<FP>(g.b_xy + (size_t)e * 2 * W + W)));
+                xyzzz_madd<FP>(a, x2, y2);
+            }
+            break;
+        case CURVE_OP_MADD_ENTRY:
+            if (!b_ident) {
+                const Fe<FP> x2 = fz_to_fe_canonical<FP>(curve_op_load<FP>(g.b_xy + (size_t)e * 2 * W));
+                const Fe<FP> y2 = fz_to_fe_canonical<FP>(curve_op_load<FP>(g.b_xy + (size_t)e * 2 * W + W));
+                xyzzz_madd_entry<FP>(a, x2, y2, (fl & CURVE_OP_NEGATE) != 0);
+                xyzzz_settle<FP>(a);
+            }
+            break;
+        default: break;
+    }
+    emit_affine<FP>(a, g.out_xy + (size_t)e * 2 * W, g.out_zero + e);
+}
+
+// ops 2, 3, 6, 7, 8: one quad per element, whole waves active (elements past the end are the identity and are not stored).
+// Every lane of a quad - of a group of quads for the wave sum - must hold the same affine result: lanes that differ from the
+// first lane of theirs are counted into *mismatch.
+template <class C>
+__global__ void __launch_bounds__(256) k_curve_op_quad(CurveOpArgs g) {
+    using FP = typename C::FP;
+    constexpr int W = FP::NL / 4;
+    const uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const int ql = threadIdx.x & 3;
+    const bool live = e < g.count;
+    const uint8_t fl = live ? g.flags[e] : 0;
+    XyzzZ<FP> a = xyzzz_identity<FP>(), b = xyzzz_identity<FP>();
+    if (live) a = curve_op_operand<FP>(g.a_xy, g.a_zero, g.a_lam, e, fl & CURVE_OP_INFLATE);
+    if (live && (g.op == CURVE_OP_ADD_Q || g.op == CURVE_OP_CHAIN_Q)) b = curve_op_operand<FP>(g.b_xy, g.b_zero, g.b_lam, e, fl & CURVE_OP_INFLATE);
+    uint32_t group = 1;  // quads that share one result
+    switch (g.op) {
+        case CURVE_OP_ADD_Q: a = xyzzz_add_q<FP>(a, b, ql); break;
+        case CURVE_OP_DBL_Q: a = xyzzz_dbl_q<FP>(a, ql); break;
+        case CURVE_OP_DBL_Q_TIMES:
+            for (uint32_t i = 0; i < g.param; ++i) a = xyzzz_dbl_q<FP>(a, ql);
+            break;
+        case CURVE_OP_WAVE_SUM_Q:
+            group = g.param;
+            a = wave_sum_q<FP>(a, (int)group, ql);
+            break;
+        default:  // CURVE_OP_CHAIN_Q: results of the quad law fed back into it
+            a = xyzzz_dbl_q<FP>(xyzzz_add_q<FP>(xyzzz_add_q<FP>(a, b, ql), a, ql), ql);
+    }
+    uint4 xy[2 * W];
+    uint8_t zero;
+    emit_affine<FP>(a, xy, &zero);
+    const int first = (int)((threadIdx.x & 63u) & ~(4u * group - 1u));  // first lane of the quad / of the group, inside the wave
+    bool same = __shfl((int)zero, first) == (int)zero;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(xy);
+#pragma unroll
+    for (int i = 0; i < 2 * FP::NL; ++i) same = same && __shfl(w[i], first) == w[i];
+    const uint32_t head = e & ~(group - 1u);  // first element of the group
+    if (head >= g.count) return;
+    if (!same) atomicAdd(g.mismatch, 1u);
+    if (e == head && ql == 0) {
+#pragma unroll
+        for (int i = 0; i < 2 * W; ++i) g.out_xy[(size_t)(e / group) * 2 * W + i] = xy[i];
+        g.out_zero[e / group] = zero;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 }  // namespace plk
@@ -1463,6 +1584,25 @@ int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t qu
     if (e == hipSuccess) e = hipMemcpy(counts, d_cnt, 32, hipMemcpyDeviceToHost);
     scratch_release(d_cnt, nullptr);
     if (e != hipSuccess) return set_error(PLK_ERR_HIP, "selftest failed: %s", hipGetErrorString(e));
+    return PLK_OK;
+}
+
+// plk_curve_op on device arrays (capi.hip has checked the ranges): d_mismatch is one zeroed word; waits for the kernel
+int curve_op_dev_impl(int curve, int op, unsigned param, uint32_t count, const void* d_a_xy, const void* d_a_zero, const void* d_a_lambda, const void* d_b_xy,
+                      const void* d_b_zero, const void* d_b_lambda, const void* d_flags, void* d_out_xy, void* d_out_zero, void* d_mismatch) {
+    if (op < 0 || op >= CURVE_OP_COUNT || count == 0) return set_error(PLK_ERR_INVALID_ARG, "bad argument");
+    CurveOpArgs g{(const uint4*)d_a_xy, (const uint4*)d_a_lambda, (const uint4*)d_b_xy, (const uint4*)d_b_lambda, (const uint8_t*)d_a_zero, (const uint8_t*)d_b_zero,
+                  (const uint8_t*)d_flags, (uint4*)d_out_xy, (uint8_t*)d_out_zero, (uint32_t*)d_mismatch, count, param, op};
+    const bool quad = curve_op_is_quad(op);
+    const unsigned blocks = (unsigned)(((size_t)count * (quad ? 4 : 1) + 255) / 256);
+    PLK_TRY(or_bad_curve(with_curve(curve, [&](auto t) {
+        using C = tag_t<decltype(t)>;
+        if (quad) k_curve_op_quad<C><<<blocks, 256>>>(g);
+        else k_curve_op_lane<C><<<blocks, 256>>>(g);
+        return PLK_OK;
+    }), curve));
+    PLK_HIP_TRY(hipGetLastError());
+    PLK_HIP_TRY(hipDeviceSynchronize());
     return PLK_OK;
 }
 

@@ -138,6 +138,7 @@ SYMBOLS = [
     ("plk_bench_ceilings", _i, [_vp, _u]),
     ("plk_msm_debug_digits", _i, [_i, _u, _sz, _vp, _vp, _vp]),
     ("plk_field_op", _i, [_i, _i, _vp, _vp, _vp, _sz]),
+    ("plk_curve_op", _i, [_i, _i, _u, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_curve_gen_bases_dev", _i, [_i, _sz, _u64, _vp, _vp, _vp, _vp]),
 ]
 

@@ -92,6 +92,7 @@ CURVE_CALLS = {
     "plk_halo_begin_tabled_dev": ((4, P, P, P, P, T, P, P, 0, 0, P, 0, 0, S, P), "null tables"),
     "plk_halo_begin": ((4, P, P, P, P, P, P, 0, P), BAD_C),
     "plk_selftest_quad": ((P, 4, 4, P), BAD_C),
+    "plk_curve_op": ((0, 0, 4, P, P, P, P, P, P, P, P, P, P), BAD_C),
     "plk_msm_debug_digits": ((8, 4, P, P, P), BAD_C),
     "plk_curve_gen_bases_dev": ((4, 0, P, P, P, S), BAD_C),
 }
