@@ -1,10 +1,13 @@
-// msm_dev.cuh -- device-side definitions shared by the translation units of the MSM (msm.hip: ordering, reduction, host side;
-// msm_acc.hip: the bucket accumulation).  The kernels are split over several files so that a change to one of them rebuilds in
-// a minute instead of five; device code is not relocatable here (no -fgpu-rdc), so anything both sides need lives in this header.
+// msm_dev.cuh -- device-side definitions shared by the translation units of the MSM (msm.hip: tables and the host side;
+// msm_order.hip: digits and the bucket ordering; msm_acc.hip: the bucket accumulation; msm_tail.hip: the reduction).  The kernels
+// are split over several files so that a change to one of them rebuilds in a minute instead of five; device code is not relocatable
+// here (no -fgpu-rdc), so anything both sides need lives in this header.  The constants and the geometry structs (OrdCfg, TailGeom)
+// are plain C++ and live in msm_geom.h, with the function that computes them.
 #pragma once
 #include "common.h"
 #include "ec.cuh"
 #include "ecz.cuh"
+#include "msm_geom.h"
 
 namespace plk {
 
@@ -63,53 +66,6 @@ template <class FP> PLK_DI XyzzZ<FP> xyzzz_load_raw(const uint4* src) {
     return r;
 }
 
-constexpr int ACC_THREADS = 128;
-
-// ---- geometry shared by the host side (msm.hip) and the kernels' translation units (msm_order.hip, msm_tail.hip) ----
-constexpr int MSM_MAX_PLANE_PARTS = 16;  // blocks per bit-plane in the reduction (planes * parts quads must fit the final block)
-constexpr int MSM_TF_MAX_WINDOW = 16;  // table-free mode: every window has its own 2^(c-1) buckets
-constexpr int MSM_MAX_WINDOW = 21;   // c - 1 <= 10 coarse + 11 fine bits in the partition (ORD_MAX_BINS, ORD_MAX_FINE)
-constexpr uint32_t CODE_INVALID = 0xFFFFFFFFu;
-constexpr int ORD_THREADS = 256;
-constexpr int ORD_TILE = 4096;      // entries staged per tile of the level-1 scatter
-constexpr int ORD_MAX_BINS = 1024;  // coarse bins
-constexpr int ORD_MAX_FINE = 11;    // fine bits: buckets per coarse bin <= 2048
-constexpr int ORD_BIN_THREADS = 512;
-constexpr uint32_t ORD_SEG = 8192;  // entries per level-2 workgroup
-constexpr int ORD_SEG_EPT = (int)(ORD_SEG / ORD_BIN_THREADS);  // ... and per thread of it
-// k_ord_bin_scatter stages a whole segment in LDS (3 fine-bit tables + the staged entries): ~74 KB, above the 64 KB a workgroup
-// gets on gfx90a / gfx942 - this library is built for gfx950 (160 KB of LDS per CU) only, plk_init refuses other devices
-static_assert(3 * (4u << ORD_MAX_FINE) + 4 * ORD_BIN_THREADS + 6 * ORD_SEG <= 160 * 1024, "k_ord_bin_scatter's LDS tile must fit a gfx950 CU");
-constexpr uint32_t ORD2_BIN_CAP = 32768;  // round 6 (k_ord_bin_sort): entries of a coarse bin that are ordered inside LDS by one workgroup (128 KiB)
-constexpr int PLANE_THREADS = 512;
-constexpr int FINAL_FUSE_WINDOWS = 4;  // up to this many tail windows are added by the last block of k_msm_final itself
-constexpr int FINAL_THREADS = 512;  // <= 8 waves, so the compiler may use 256 VGPRs: the point arithmetic must not spill
-constexpr int COMBINE_THREADS = 512;
-
-struct OrdCfg {
-    int c;                   // window bits
-    int windows;             // digits per scalar
-    uint32_t window_buckets; // table-free mode: 2^(c-1) (every window has its own bucket range), else 0
-    int fine_bits;           // bucket id = [coarse bin | fine]
-    int nbins;               // coarse bins in use
-    uint32_t spt;            // scalars per sub-tile (<= ORD_THREADS, spt * windows <= ORD_TILE)
-    uint32_t sub;            // sub-tiles per tile (one block walks them in turn)
-    uint32_t nt1;            // tiles
-    int raw_signed;          // 1: the "scalars" are half scalars of a GLV split: canonical magnitude, sign in bit 255 (glv.cuh)
-    uint32_t entries_cap;    // n_eff * windows: size of tmp[] / sorted[] and of the table (checked build)
-    uint32_t ent_stride;     // entry id of (window j, scalar i) = j * ent_stride + ent_first + i: the table index.  ent_stride = n_eff of the
-    uint32_t ent_first;      // context; ent_first > 0 when the scalars belong to generators first .. first + n - 1 only (plk_msm_execute_parts_dev)
-    // round 6: 1 = the tile-major level 1 (k_ord_tiles, msm_order.hip) with the coarse bin taken from the LOW bits of the bucket id: the
-    // buckets are ordered (and numbered, for everything downstream) by v = [low coarse bits | high fine bits] of the digit's bucket
-    // b = |d| - 1, so that a short top window - whose digits are all small - spreads over every bin instead of filling the first few.
-    // The reduction reads the weight of v off its two halves (TailGeom::transposed).
-    int perm;
-    // round 6: only entries whose coarse bin lies in [bin_lo, bin_hi) are kept (0, nbins: all of them).  A rank of a device group that
-    // takes a BUCKET range of a sharded vector - every rank reads the whole vector and keeps its N-th of the bins - orders, accumulates
-    // and reduces an N-th of the entries over an N-th of the buckets (plk_msm_execute_parts_buckets_dev).
-    uint32_t bin_lo, bin_hi;
-};
-
 constexpr int TAIL_MAX = 16;
 struct TailSlot {
     const uint32_t* off;  // bucket offsets off[buckets + 1]
@@ -136,28 +92,12 @@ struct TailBatch {
     TailSlot s[TAIL_MAX];
 };
 
-constexpr uint32_t HEAD_NONE = 0xFFFFFFFFu;
-constexpr uint32_t HEAVY_HEADS = 32;   // more head pieces than this PER LANE of k_msm_assemble (2^lpb_log lanes per bucket): the bucket is summed by workgroups
-constexpr uint32_t HEAVY_CHUNK = 2048;
-
-// what the reduction's launches need of a context (msm_tail.hip: msm_launch_reduce_stage)
-struct TailGeom {
-    uint32_t buckets, heavy_cap, tail_wbuckets;
-    uint32_t max_lanes;  // upper bound of the accumulation lanes of an execution (k_msm_heads is launched for it)
-    int lpb_log, two_level, L, H, g_log, lpl_log, table_free, windows, tail_windows, plane_blocks, planes, tail_shift;
-    // 1: bucket slot v = lo * 2^H + hi holds the bucket of weight hi * 2^L + lo + 1 (OrdCfg::perm): the grid in memory is 2^L rows of
-    // 2^H slots, its ROW sums are the column sums C_lo of the weighting and its column sums the row sums R_hi
-    int transposed;
-    // 1: some vector of the batch is a BUCKET share (OrdCfg::bin_lo / bin_hi): its entries are spread over all the accumulation lanes in
-    // chains shorter than a bucket, so most lanes end inside a bucket and the list of live head pieces is long - k_msm_heads gets a wide grid
-    int many_heads;
-};
 // the buffers of one ordering (msm_order.hip: msm_launch_order_stage)
 struct OrdBuffers {
     const void* scalars;
     size_t n;
     void *cnt1, *tmp, *sorted, *cnt2, *off;
-    uint32_t *bin_total, *bin_base, *seg_base, *done_counter;
+    uint32_t* meta;  // META_* (msm_geom.h)
     uint32_t chunk, lanes, buckets;
 };
 // the guard counters of a translation unit (-DPLK_CHECKED), read back for plk_checked_failures

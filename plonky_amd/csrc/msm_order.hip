@@ -910,18 +910,19 @@ template <class C> int msm_launch_glv_split(const void* d_scalars, size_t n, voi
     return PLK_OK;
 }
 // stage 0: level-1 counts + scan (and this execution's chunk length); 1: level-1 scatter; 2: level 2 (skipped by one-level orderings)
-// the tile-major level 1 (round 6): where msm_configure set OrdCfg::perm
+// the tile-major level 1 (round 6): where msm_geometry set OrdCfg::perm
 static bool order_tiles2(const OrdCfg& o) { return o.perm != 0; }
 template <class C> int msm_launch_order_stage(int stage, const OrdCfg& o, const OrdBuffers& b, hipStream_t stream) {
     const bool one_level = o.fine_bits == 0;
+    uint32_t *const bin_total = b.meta + META_BIN_TOTAL, *const bin_base = b.meta + META_BIN_BASE, *const seg_base = b.meta + META_SEG_BASE;
     if (order_tiles2(o)) {
         const uint32_t cap = (uint32_t)ORD2_TS * (uint32_t)o.windows;
         if (stage == 0) {
             const size_t lds = (size_t)cap * 4;
             // more than 64 KiB of LDS in all (42 KiB static + the tile's records): asked for per kernel, as the transform's launches do
             (void)hipFuncSetAttribute((const void*)k_ord_tiles<C>, hipFuncAttributeMaxDynamicSharedMemorySize, ORD2_TS * ORD2_MAX_WINDOWS * 4);
-            k_ord_tiles<C><<<o.nt1, ORD2_THREADS, lds, stream>>>((const uint4*)b.scalars, b.n, o, (uint32_t*)b.cnt1, b.bin_total, (uint32_t*)b.tmp);
-            k_ord_scan_bins<<<1, 256, 0, stream>>>(b.bin_total, o.nbins, b.bin_base, b.seg_base, b.done_counter + 2, b.chunk, b.lanes, ORD2_BIN_CAP);
+            k_ord_tiles<C><<<o.nt1, ORD2_THREADS, lds, stream>>>((const uint4*)b.scalars, b.n, o, (uint32_t*)b.cnt1, bin_total, (uint32_t*)b.tmp);
+            k_ord_scan_bins<<<1, 256, 0, stream>>>(bin_total, o.nbins, bin_base, seg_base, b.meta + META_DYN_CHUNK, b.chunk, b.lanes, ORD2_BIN_CAP);
         } else if (stage == 2) {
             // hot bins hold more than ORD2_BIN_CAP entries each: at most entries / ORD2_BIN_CAP of them, entries / ORD_SEG + that many segments
             const size_t entries = b.n * (size_t)o.windows;
@@ -933,19 +934,19 @@ template <class C> int msm_launch_order_stage(int stage, const OrdCfg& o, const 
             static const bool no_cache = getenv("PLK_MSM_BINSORT_NOCACHE") != nullptr;
             if (o.nt1 <= 1024u && !no_cache) {
                 (void)hipFuncSetAttribute((const void*)k_ord_bin_sort<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-                k_ord_bin_sort<true><<<o.nbins, ORD2_SORT_THREADS, lds_b, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, b.bin_base, o.fine_bits,
+                k_ord_bin_sort<true><<<o.nbins, ORD2_SORT_THREADS, lds_b, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, bin_base, o.fine_bits,
                                                                                    o.nbins, b.buckets, (uint32_t*)b.off, (uint32_t*)b.sorted, o.entries_cap, o.ent_stride,
                                                                                    o.ent_first);
             } else {
                 (void)hipFuncSetAttribute((const void*)k_ord_bin_sort<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-                k_ord_bin_sort<false><<<o.nbins, ORD2_SORT_THREADS, lds_b, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, b.bin_base, o.fine_bits,
+                k_ord_bin_sort<false><<<o.nbins, ORD2_SORT_THREADS, lds_b, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, bin_base, o.fine_bits,
                                                                                     o.nbins, b.buckets, (uint32_t*)b.off, (uint32_t*)b.sorted, o.entries_cap, o.ent_stride,
                                                                                     o.ent_first);
             }
             const unsigned hot_grid = segs < 512u ? segs : 512u;
-            k_ord_bin_count2<<<hot_grid, ORD_BIN_THREADS, lds, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, b.bin_base, b.seg_base, o.fine_bits,
+            k_ord_bin_count2<<<hot_grid, ORD_BIN_THREADS, lds, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, bin_base, seg_base, o.fine_bits,
                                                                    o.nbins, (uint32_t*)b.cnt2);
-            k_ord_bin_scatter2<<<hot_grid, ORD_BIN_THREADS, lds_s, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, b.bin_base, b.seg_base,
+            k_ord_bin_scatter2<<<hot_grid, ORD_BIN_THREADS, lds_s, stream>>>((const uint32_t*)b.tmp, (const uint32_t*)b.cnt1, o.nt1, cap, bin_base, seg_base,
                                                                                o.fine_bits, o.nbins, b.buckets, (const uint32_t*)b.cnt2, (uint32_t*)b.off,
                                                                                (uint32_t*)b.sorted, o.entries_cap, o.ent_stride, o.ent_first);
         }
@@ -954,17 +955,17 @@ template <class C> int msm_launch_order_stage(int stage, const OrdCfg& o, const 
     }
     if (stage == 0) {
         k_ord_count<C><<<o.nt1, ORD_THREADS, 0, stream>>>((const uint4*)b.scalars, b.n, o, (uint32_t*)b.cnt1);
-        k_ord_scan1<<<o.nbins, 256, 0, stream>>>((uint32_t*)b.cnt1, o.nt1, o.nbins, b.bin_total, b.bin_base, b.seg_base, b.done_counter, b.done_counter + 2,
+        k_ord_scan1<<<o.nbins, 256, 0, stream>>>((uint32_t*)b.cnt1, o.nt1, o.nbins, bin_total, bin_base, seg_base, b.meta + META_DONE, b.meta + META_DYN_CHUNK,
                                                  b.chunk, b.lanes, one_level ? (uint32_t*)b.off : nullptr);
     } else if (stage == 1) {
-        k_ord_scatter<C><<<o.nt1, ORD_THREADS, 0, stream>>>((const uint4*)b.scalars, b.n, o, (const uint32_t*)b.cnt1, b.bin_base, (uint2*)b.tmp,
+        k_ord_scatter<C><<<o.nt1, ORD_THREADS, 0, stream>>>((const uint4*)b.scalars, b.n, o, (const uint32_t*)b.cnt1, bin_base, (uint2*)b.tmp,
                                                             one_level ? (uint32_t*)b.sorted : nullptr);
     } else if (!one_level) {
         // the number of segments is only known on the device: launch for the upper bound (+ nbins blocks that write the
         // offsets of the empty bins), blocks past the end exit
         const unsigned segs = (unsigned)(b.n * (size_t)o.windows / ORD_SEG + o.nbins + 1);
-        k_ord_bin_count<<<segs, ORD_BIN_THREADS, 0, stream>>>((const uint2*)b.tmp, b.bin_base, b.seg_base, o.fine_bits, o.nbins, (uint32_t*)b.cnt2);
-        k_ord_bin_scatter<<<segs + o.nbins, ORD_BIN_THREADS, 0, stream>>>((const uint2*)b.tmp, b.bin_base, b.seg_base, o.fine_bits, o.nbins, b.buckets,
+        k_ord_bin_count<<<segs, ORD_BIN_THREADS, 0, stream>>>((const uint2*)b.tmp, bin_base, seg_base, o.fine_bits, o.nbins, (uint32_t*)b.cnt2);
+        k_ord_bin_scatter<<<segs + o.nbins, ORD_BIN_THREADS, 0, stream>>>((const uint2*)b.tmp, bin_base, seg_base, o.fine_bits, o.nbins, b.buckets,
                                                                           (const uint32_t*)b.cnt2, (uint32_t*)b.off, (uint32_t*)b.sorted, o.entries_cap);
     }
     PLK_HIP_TRY(hipGetLastError());
