@@ -185,6 +185,34 @@ int plk_poly_division(int field, const uint64_t* a, size_t la, const uint64_t* b
 /* The fold of plonk.rs:207-215: out[0..k] = coefficients of prod_{i < k} (X - roots[i]), monic; k = 0 gives [1];
  * k <= PLK_POLY_DIV_MAX_DEGREE.  Host pointers, computed on the host (at most k^2 / 2 products): no launch. */
 int plk_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out);
+/* Polynomial::inv_mod_xn (polynomial.rs:261-294) and Polynomial::polynomial_division (polynomial.rs:299-327) for a divisor of ANY
+ * degree, by the reference's Newton route (polydiv_newton.hip).  Like the Plookup and sigma entries these four take a SIZE first and
+ * the field id second.  Fields: the five 4-limb fields; anything else is PLK_ERR_INVALID_ARG.  Elements: 4 limbs, Montgomery form;
+ * every element written is fully reduced, and the inverse, the quotient and the remainder are unique: the words are the reference's.
+ * plk_poly_inv_mod_xn_dev: d_out[0 .. n) = g with g h = 1 mod X^n.  n >= 1, lh >= 1; only h[0 .. min(lh, n)) is read, a shorter h reads
+ * as zero-padded.  h[0] == 0 (the reference panics, "Inverse doesn't exist."): bit 0 of *d_status is set and d_out is unspecified;
+ * nothing is read or written out of bounds.
+ * plk_poly_div_rem_dev: a = q b + rem, deg rem < deg b.  d_a: la coefficients, leading zero coefficients are allowed; d_b: lb
+ * coefficients ON THE DEVICE (it can be as long as a), degree k = lb - 1 >= 1, la > k, b need not be monic.  d_q: q_len >= la - k elements,
+ * the la - k quotient coefficients followed by zeros (the convention of plk_poly_division_dev).  d_rem (nullable): k elements, the remainder
+ * zero-padded.  b[k] == 0: bit 1 of *d_status is set and the outputs are unspecified.
+ * d_status (nullable: nothing is reported then): ONE device word, written in stream order by a kernel.  The bits are OR-ed into what
+ * the caller initialised the word to (the convention of the sigma and Plookup status words): zero it before the call to read "zero
+ * on success".
+ * Both are asynchronous on `stream` and synchronise nothing: every size follows from n, la, lb alone.  Inputs are unchanged; working
+ * memory comes from the library's scratch pool (the first call for a transform size builds and caches the transform's tables, as every
+ * transform does); an output that overlaps an input (or d_rem overlapping d_q) is PLK_ERR_INVALID_ARG.  The transforms have
+ * 2^ceil(log2(2 (la - k))) points (2^ceil(log2(2 n)) for the inverse; about k + min(la - k, k) for the remainder): a size beyond the
+ * field's 2-adicity or beyond 2^30 is PLK_ERR_INVALID_ARG before anything is launched.  plk_poly_div_rem_dev takes the Newton route
+ * for every k >= 1 (b is on the device; reading it back would synchronise). */
+int plk_poly_inv_mod_xn_dev(size_t n, int field, const void* d_h, size_t lh, void* d_out, uint32_t* d_status, void* stream);
+/* Same with host pointers; h[0] == 0 is PLK_ERR_INVALID_ARG with plk_last_error() starting "Inverse doesn't exist". */
+int plk_poly_inv_mod_xn(size_t n, int field, const uint64_t* h, size_t lh, uint64_t* out);
+int plk_poly_div_rem_dev(size_t la, int field, const void* d_a, const void* d_b, size_t lb, void* d_q, size_t q_len, void* d_rem, uint32_t* d_status,
+                         void* stream);
+/* Same with host pointers; b[k] == 0 is PLK_ERR_INVALID_ARG.  A divisor of degree k <= PLK_POLY_DIV_MAX_DEGREE goes the recurrence route
+ * of plk_poly_division (b is on the host), a larger one the Newton route: the same words either way. */
+int plk_poly_div_rem(size_t la, int field, const uint64_t* a, const uint64_t* b, size_t lb, uint64_t* q, size_t q_len, uint64_t* rem);
 
 /* ---- the Plonk quotient numerator  (src/plonk.rs, src/gates/) ------------------------------------ */
 /* The 8n-point loop of Prover::vanishing_poly (plonk.rs:392-453): for every point x = g^i of the 8n domain the

@@ -218,6 +218,33 @@ def polynomial_division(field, a, b):
     return q, r[: _degree_plus_one(r)].copy()
 
 
+def polynomial_inv_mod_xn(field, h, n):
+    """Polynomial::inv_mod_xn (polynomial.rs:261-294): g with g h = 1 mod X^n -> (n, 4); h[0] == 0 raises as the reference panics."""
+    x = _elems(field, h)
+    assert n >= 1 and x.shape[0] >= 1
+    if not x[0].any():
+        raise ValueError("Inverse doesn't exist.")
+    out = np.empty((n, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_poly_inv_mod_xn(n, field, _ptr(x), x.shape[0], _ptr(out)))
+    return out
+
+
+def polynomial_div_rem(field, a, b):
+    """Polynomial::polynomial_division (polynomial.rs:299-327) -> (q, r) for a divisor of ANY degree (plk_poly_div_rem: the recurrence of
+    polynomial_division up to degree 32, the reference's Newton route above), with the reference's lengths in every branch, the branches
+    of polynomial_division: a zero a gives ([0], empty), deg a < deg b gives ([0], a), deg b = 0 gives a / b[0] untrimmed and an empty
+    remainder, otherwise q and r trimmed.  A zero b raises ZeroDivisionError (the reference panics)."""
+    x, y = _elems(field, a), _elems(field, b)
+    da, db = _degree_plus_one(x), _degree_plus_one(y)
+    if db == 0 or da < db or db == 1:
+        return polynomial_division(field, x, y)  # no divisor degree is involved in these branches
+    xs, ys = np.ascontiguousarray(x[:da]), np.ascontiguousarray(y[:db])
+    q = np.empty((da - db + 1, 4), dtype=np.uint64)
+    r = np.empty((db - 1, 4), dtype=np.uint64)
+    _lib.check(_lib.load().plk_poly_div_rem(da, field, _ptr(xs), _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
+    return q, r[: _degree_plus_one(r)].copy()
+
+
 def polynomial_long_division(field, a, b):
     """Polynomial::polynomial_long_division (polynomial.rs:232-259): the same quotient and remainder; its deg b = 0 case goes through
     the loop and leaves the quotient at deg a + 1 coefficients."""

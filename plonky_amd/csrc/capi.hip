@@ -728,6 +728,60 @@ int plk_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* 
     return poly_from_roots_impl(field, k, roots, out);
 }
 
+// ---- the power-series inverse and the division by a divisor of any degree (polydiv_newton.hip) ----
+int plk_poly_inv_mod_xn_dev(size_t n, int field, const void* d_h, size_t lh, void* d_out, uint32_t* d_status, void* stream) {
+    PLK_API;
+    return poly_inv_mod_xn_dev_impl(n, field, d_h, lh, d_out, d_status, as_stream(stream));
+}
+static bool limbs4_zero(const uint64_t* x) { return !(x[0] | x[1] | x[2] | x[3]); }
+int plk_poly_inv_mod_xn(size_t n, int field, const uint64_t* h, size_t lh, uint64_t* out) {
+    PLK_API;
+    PLK_TRY(poly_inv_mod_xn_check(n, field, lh));
+    if (!h || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer: h / out");
+    if (limbs4_zero(h)) return set_error(PLK_ERR_INVALID_ARG, "Inverse doesn't exist: h[0] is zero");
+    if (lh > n) lh = n;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(h, lh * 32);
+    c.pin(out, n * 32);
+    void *dh = nullptr, *dout = nullptr;
+    PLK_TRY(c.in(dh, h, lh * 32));
+    PLK_TRY(c.tmp(dout, n * 32));
+    PLK_TRY(poly_inv_mod_xn_dev_impl(n, field, dh, lh, dout, nullptr, c.stream()));
+    PLK_TRY(c.out(out, dout, n * 32));
+    return c.finish();
+}
+int plk_poly_div_rem_dev(size_t la, int field, const void* d_a, const void* d_b, size_t lb, void* d_q, size_t q_len, void* d_rem, uint32_t* d_status,
+                         void* stream) {
+    PLK_API;
+    return poly_div_rem_dev_impl(la, field, d_a, d_b, lb, d_q, q_len, d_rem, d_status, as_stream(stream));
+}
+int plk_poly_div_rem(size_t la, int field, const uint64_t* a, const uint64_t* b, size_t lb, uint64_t* q, size_t q_len, uint64_t* rem) {
+    PLK_API;
+    PLK_TRY(poly_div_rem_check(la, field, lb, q_len, rem != nullptr));
+    if (!a || !b || !q) return set_error(PLK_ERR_INVALID_ARG, "null pointer: a / b / q");
+    const size_t k = lb - 1;
+    if (limbs4_zero(b + 4 * k)) return set_error(PLK_ERR_INVALID_ARG, "the leading coefficient b[%zu] is zero", k);
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(a, la * 32);
+    c.pin(b, lb * 32);
+    c.pin(q, q_len * 32);
+    void *da = nullptr, *db = nullptr, *dq = nullptr, *drem = nullptr;
+    PLK_TRY(c.in(da, a, la * 32));
+    PLK_TRY(c.tmp(dq, q_len * 32));
+    PLK_TRY(c.tmp(drem, k * 32));
+    if (k <= PLK_POLY_DIV_MAX_DEGREE) {  // b is on the host: the recurrence route (polydiv.hip) gives the same words
+        PLK_TRY(poly_division_dev_impl(field, da, la, b, lb, dq, q_len, drem, c.stream()));
+    } else {
+        PLK_TRY(c.in(db, b, lb * 32));
+        PLK_TRY(poly_div_rem_dev_impl(la, field, da, db, lb, dq, q_len, rem ? drem : nullptr, nullptr, c.stream()));
+    }
+    PLK_TRY(c.out(q, dq, q_len * 32));
+    if (rem) PLK_TRY(c.out(rem, drem, k * 32));
+    return c.finish();
+}
+
 // ---- the Plonk quotient numerator ----
 int plk_plonk_vanishing_points_dev(int field, unsigned log_degree, const void* d_constants_8n, const void* d_wires_8n, const void* d_s_sigma_8n,
                                    const void* d_plonk_z_8n, const uint64_t* k_is, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma,

@@ -211,6 +211,13 @@ int halo_s_dev_impl(int field, unsigned k, const uint64_t* us, void* d_out, hipS
 int poly_division_check(int field, size_t la, const uint64_t* b, size_t lb, size_t q_len);
 int poly_division_dev_impl(int field, const void* d_a, size_t la, const uint64_t* b, size_t lb, void* d_q, size_t q_len, void* d_rem, hipStream_t stream);
 int poly_from_roots_impl(int field, unsigned k, const uint64_t* roots, uint64_t* out);
+// the power-series inverse and the division by a divisor of any degree (polydiv_newton.hip): size first, then the field id; b is a
+// DEVICE array; the checks hold the refusals the host entries share
+int poly_inv_mod_xn_check(size_t n, int field, size_t lh);
+int poly_inv_mod_xn_dev_impl(size_t n, int field, const void* d_h, size_t lh, void* d_out, uint32_t* d_status, hipStream_t stream);
+int poly_div_rem_check(size_t la, int field, size_t lb, size_t q_len, bool want_rem);
+int poly_div_rem_dev_impl(size_t la, int field, const void* d_a, const void* d_b, size_t lb, void* d_q, size_t q_len, void* d_rem, uint32_t* d_status,
+                          hipStream_t stream);
 int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_constants, const void* d_local, const void* d_right, const void* d_below,
                                    const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_out, hipStream_t stream);
 

@@ -442,6 +442,40 @@ def polynomial_division_dev(field, a, b, q_len=None, out=None, rem=None):
     return out, rem
 
 
+# ---- the series inverse and the division by a divisor of any degree (polydiv_newton.hip): everything stays on the device ----
+def _status_ptr(status):
+    if status is None:
+        return None
+    assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1 and status.is_contiguous()
+    return ctypes.c_void_p(status.data_ptr())
+
+
+def polynomial_inv_mod_xn_dev(field, h, n, out=None, status=None):
+    """plk_poly_inv_mod_xn_dev: h (lh, 4) int64 CUDA tensor -> g (n, 4) with g h = 1 mod X^n.  status (optional): an int32 CUDA tensor of
+    one word; bit 0 is OR-ed in when h[0] == 0 (g is unspecified then).  Nothing is synchronised."""
+    assert h.is_cuda and h.dtype == torch.int64 and h.is_contiguous() and h.dim() == 2 and h.shape[1] == 4
+    out = _out_tensor(out, (n, 4), h.device)
+    _lib.check(_lib.load().plk_poly_inv_mod_xn_dev(n, field, ctypes.c_void_p(h.data_ptr()), h.shape[0], ctypes.c_void_p(out.data_ptr()), _status_ptr(status),
+                                                   _stream()))
+    return out
+
+
+def polynomial_div_rem_dev(field, a, b, q_len=None, out=None, rem=None, status=None):
+    """plk_poly_div_rem_dev: a (la, 4) and b (lb, 4) int64 CUDA tensors, k = lb - 1 >= 1 of ANY size below la -> (q, rem): q (q_len, 4),
+    the quotient followed by zeros (q_len defaults to la - k), rem (k, 4).  status (optional): an int32 CUDA tensor of one word; bit 1 is
+    OR-ed in when b[k] == 0 (the outputs are unspecified then).  Nothing is synchronised."""
+    for t in (a, b):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4
+    la, k = a.shape[0], b.shape[0] - 1
+    if q_len is None:
+        q_len = out.shape[0] if out is not None else max(la - k, 0)
+    out = _out_tensor(out, (q_len, 4), a.device)
+    rem = _out_tensor(rem, (max(k, 0), 4), a.device)
+    _lib.check(_lib.load().plk_poly_div_rem_dev(la, field, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), b.shape[0],
+                                                ctypes.c_void_p(out.data_ptr()), q_len, ctypes.c_void_p(rem.data_ptr()), _status_ptr(status), _stream()))
+    return out, rem
+
+
 def public_input_quotient_dev(field, wire_polys_no_pis, alpha, roots, degree):
     """The public-input quotient of plonk.rs:199-235: scale_polynomials(wire polynomials without public inputs, alpha, degree) divided
     by prod (X - roots[i]) over the public-input rows -> (quotient padded to `degree`, remainder (k, 4): zero for a valid witness).

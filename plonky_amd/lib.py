@@ -53,6 +53,11 @@ SYMBOLS = [
     ("plk_poly_division_dev", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     ("plk_poly_division", _i, [_i, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     ("plk_poly_from_roots", _i, [_i, _u, _vp, _vp]),
+    # the series inverse and the general division take a size first (_sz) and the field id second
+    ("plk_poly_inv_mod_xn_dev", _i, [_sz, _i, _vp, _sz, _vp, _vp, _vp]),
+    ("plk_poly_inv_mod_xn", _i, [_sz, _i, _vp, _sz, _vp]),
+    ("plk_poly_div_rem_dev", _i, [_sz, _i, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    ("plk_poly_div_rem", _i, [_sz, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     ("plk_plonk_vanishing_points_dev", _i, [_i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_vanishing_points", _i, [_i, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("plk_plonk_permutation_z_dev", _i, [_i, _u, _vp, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp]),
