@@ -520,6 +520,40 @@ int plk_hash_field_to_curve_dev(size_t count, int curve, const void* d_seeds, vo
  * The seam that separates a wrong hash from a wrong root.  Host pointers. */
 int plk_blake_field(size_t count, int field, const uint8_t* iters, const uint64_t* seeds, uint64_t* out_x, uint8_t* out_y_neg);
 
+/* ---- Rescue: the permutation under the Challenger, the sponge, k-th roots  (src/rescue.rs, src/mds.rs, field.rs:340-375) ----------- */
+/* A context holds what rescue_permutation::<F>(state, security_bits) (rescue.rs:70-88) needs besides the state: the field, the width
+ * W, the number of rounds, and in device memory the round constants, the MDS matrix and the exponent of 1 / F::ALPHA.  `constants`
+ * are rounds x 2 x W elements, step A then step B per round, as generate_rescue_constants (rescue.rs:97-121) returns them, L limbs
+ * each, Montgomery form: the caller hands them over, the library does not restate the reference's ChaCha8Rng stream.  ALPHA is 5, and
+ * 11 on Bls12377Scalar (field/bls12_377_scalar.rs:169).  The context lives on the calling thread's device.  Only W = 4
+ * (RESCUE_SPONGE_WIDTH, plonk.rs) is built: any other width, rounds == 0, an unknown field id or a null pointer is
+ * PLK_ERR_INVALID_ARG.  These entries take a COUNT or a SIZE first and the context / field id second, as every entry added after the
+ * pinned id-first set does: plk_rescue_create and plk_rescue_mds start with the width. */
+typedef struct plk_rescue_ctx plk_rescue_ctx;
+int plk_rescue_create(size_t width, int field, size_t rounds, const uint64_t* constants, plk_rescue_ctx** out);
+int plk_rescue_free(plk_rescue_ctx* ctx);
+/* recommended_rounds::<F>(width, security_bits) (rescue.rs:123-125): max(10, ceil(security_bits / (2 width))). */
+int plk_rescue_rounds(size_t width, size_t security_bits, size_t* rounds);
+/* mds_matrix::<F>(width) (mds.rs:56-77): out = width x width elements, row-major, M[r][c] = 1 / ((width + r) - c), Montgomery limbs.
+ * Host pointer; width 4 only. */
+int plk_rescue_mds(size_t width, int field, uint64_t* out);
+/* rescue_permutation (rescue.rs:70-88) of `count` states: states and out are count x W x L limbs, row-major, Montgomery form, fully
+ * reduced.  One state per four adjacent lanes.  The _dev form is asynchronous on `stream` and runs on the calling thread's device,
+ * which must be the context's; d_out == d_states is allowed.  count == 0 is PLK_OK and launches nothing; count < 2^32. */
+int plk_rescue_permutation(size_t count, const plk_rescue_ctx* ctx, const uint64_t* states, uint64_t* out);
+int plk_rescue_permutation_dev(size_t count, const plk_rescue_ctx* ctx, const void* d_states, void* d_out, void* stream);
+/* rescue_sponge(inputs, n_outputs, security_bits) (rescue.rs:40-68) of `count` input rows: rate 3, capacity 1, state zero; chunks of
+ * three inputs are added to state[0..3] with one permutation per chunk (n_inputs == 0: none), then state[0..3] is squeezed with a
+ * permutation after every three outputs.  inputs: count x n_inputs x L limbs, out: count x n_outputs x L.  rescue_hash_n_to_1 / 2 / 3
+ * (rescue.rs:26-38) are n_outputs = 1 / 2 / 3.  One launch per call.  n_outputs == 0 is PLK_ERR_INVALID_ARG. */
+int plk_rescue_sponge(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const uint64_t* inputs, size_t n_outputs, uint64_t* out);
+int plk_rescue_sponge_dev(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const void* d_inputs, size_t n_outputs, void* d_out, void* stream);
+/* Field::kth_root_u32(k) (field.rs:340-375) per element: x^d with d = ((p + n (p - 1)) / k) mod (p - 1) for the first n in 1 ..= k
+ * that makes the division exact; 0 maps to 0.  The witness of a RescueStepAGate (gates/rescue_a.rs:132).  k == 0, and a k with
+ * gcd(k, p - 1) != 1 (the reference panics: "not permutations in this field"), are PLK_ERR_INVALID_ARG.  In place is allowed. */
+int plk_field_kth_root(size_t count, int field, uint32_t k, const uint64_t* in, uint64_t* out);
+int plk_field_kth_root_dev(size_t count, int field, uint32_t k, const void* d_in, void* d_out, void* stream);
+
 /* r = log_inputs rounds of that fold at once, in the scaled form halo.hip keeps its generators in:
  *     out_i = g_i + sum_{t = 1 .. 2^r - 1} [s_t] g_{i + t n_out},   i < n_out,
  * g = 2^r n_out affine points (+ optional identity flags), the 2^r scalars in DEVICE memory (4 limbs each, Montgomery, scalar

@@ -964,3 +964,172 @@ def pedersen_generators(curve, degree):
     """circuit_builder.rs:1127-1129: (g[0 .. degree), h = the point of seed degree, u = the point of seed degree + 1)."""
     pts = blake_hash_usize_to_curve(curve, 0, degree + 2)
     return pts[:degree], pts[degree], pts[degree + 1]
+
+
+# ---- Rescue: the permutation, the sponge, k-th roots and the Challenger (rescue.rs, mds.rs, field.rs:340-375, plonk_challenger.rs) ----
+RESCUE_SPONGE_WIDTH, RESCUE_SPONGE_RATE = 4, 3
+
+
+def _refused(rc):
+    if rc == _lib.PLK_ERR_INVALID_ARG:
+        raise ValueError(_lib.load().plk_last_error().decode())
+    _lib.check(rc)
+
+
+def rescue_rounds(width, security_bits):
+    """recommended_rounds (rescue.rs:123-125)."""
+    r = ctypes.c_size_t(0)
+    _refused(_lib.load().plk_rescue_rounds(int(width), int(security_bits), ctypes.byref(r)))
+    return int(r.value)
+
+
+def rescue_mds(field, width=RESCUE_SPONGE_WIDTH):
+    """mds_matrix::<F>(width) (mds.rs:56-77): (width, width, L) Montgomery limbs."""
+    out = np.empty((width, width, _FIELD_LIMBS.get(field, 4)), dtype=np.uint64)
+    _refused(_lib.load().plk_rescue_mds(int(width), field, _ptr(out)))
+    return out
+
+
+class RescueContext:
+    """What rescue_permutation needs besides the state: field, width, rounds and, on the device, the round constants, the MDS matrix
+    and the exponent of 1 / ALPHA.  constants: (rounds, 2, width, L) Montgomery limbs, step A then step B per round, as
+    generate_rescue_constants (rescue.rs:97-121) returns them - the caller brings them (the reference draws them from
+    ChaCha8Rng::seed_from_u64(1337), which is not restated here)."""
+
+    def __init__(self, field, constants, width=RESCUE_SPONGE_WIDTH, rounds=None):
+        L = _FIELD_LIMBS.get(field, 4)
+        c = np.ascontiguousarray(constants, dtype=np.uint64)
+        if rounds is None:
+            rounds = c.size // (2 * width * L) if width else 0
+        assert c.size == rounds * 2 * width * L, "constants: rounds x 2 x width elements"
+        self.field, self.width, self.rounds = field, int(width), int(rounds)
+        self._ctx = ctypes.c_void_p()
+        _refused(_lib.load().plk_rescue_create(self.width, field, self.rounds, _ptr(c), ctypes.byref(self._ctx)))
+
+    @property
+    def handle(self):
+        assert self._ctx is not None and self._ctx.value, "the context has been freed"
+        return self._ctx
+
+    def free(self):
+        if self._ctx is not None and self._ctx.value:
+            _lib.check(_lib.load().plk_rescue_free(self._ctx))
+        self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def rescue_permutation(ctx, states):
+    """rescue_permutation (rescue.rs:70-88) per state: (n, 4, L) or (4, L) Montgomery limbs -> the same shape."""
+    a = np.ascontiguousarray(states, dtype=np.uint64)
+    L = _FIELD_LIMBS[ctx.field]
+    assert a.shape[-2:] == (ctx.width, L)
+    out = np.empty_like(a)
+    _refused(_lib.load().plk_rescue_permutation(a.size // (ctx.width * L), ctx.handle, _ptr(a), _ptr(out)))
+    return out
+
+
+def rescue_sponge(ctx, inputs, num_outputs):
+    """rescue_sponge (rescue.rs:40-68) per row: inputs (n, n_inputs, L) or (n_inputs, L) -> (n, num_outputs, L) or (num_outputs, L)."""
+    L = _FIELD_LIMBS[ctx.field]
+    a = np.ascontiguousarray(inputs, dtype=np.uint64)
+    single = a.ndim == 2
+    a = a.reshape((1,) + a.shape) if single else a
+    assert a.ndim == 3 and a.shape[2] == L
+    out = np.empty((a.shape[0], int(num_outputs), L), dtype=np.uint64)
+    _refused(_lib.load().plk_rescue_sponge(a.shape[0], ctx.handle, a.shape[1], _ptr(a), int(num_outputs), _ptr(out)))
+    return out[0] if single else out
+
+
+def rescue_hash_n_to_1(ctx, inputs):  # rescue.rs:26-28
+    return rescue_sponge(ctx, inputs, 1)
+
+
+def rescue_hash_n_to_2(ctx, inputs):  # rescue.rs:30-33
+    return rescue_sponge(ctx, inputs, 2)
+
+
+def rescue_hash_n_to_3(ctx, inputs):  # rescue.rs:35-38
+    return rescue_sponge(ctx, inputs, 3)
+
+
+def kth_root(field, x, k):
+    """Field::kth_root_u32(k) (field.rs:340-375) per element of x ((n, L) Montgomery limbs); ValueError where the reference panics."""
+    a = np.ascontiguousarray(x, dtype=np.uint64)
+    out = np.empty_like(a)
+    _refused(_lib.load().plk_field_kth_root(a.size // _FIELD_LIMBS.get(field, 4), field, int(k), _ptr(a), _ptr(out)))
+    return out
+
+
+class Challenger:
+    """Challenger<F> (plonk_challenger.rs:20-109) over a RescueContext; elements are (L,) arrays of Montgomery limbs.  Every
+    permutation is one rescue_permutation call of count 1: a transcript is a latency chain, the device pays for batches.
+
+    The mirror is literal, including two things the reference does that a reader may take for slips and that are NOT repaired here:
+    get_challenge pops from the END of the output buffer (state[2] first), and absorb_buffered_inputs refills the output buffer
+    from state[0..3] on every call, also with nothing buffered - so challenges drawn with no observation in between are the same
+    element (get_2_challenges returns two equal values)."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.sponge_state = np.zeros((RESCUE_SPONGE_WIDTH, _FIELD_LIMBS[ctx.field]), dtype=np.uint64)
+        self.input_buffer = []
+        self.output_buffer = []
+
+    def clone(self):
+        c = Challenger(self.ctx)
+        c.sponge_state = self.sponge_state.copy()
+        c.input_buffer = [e.copy() for e in self.input_buffer]
+        c.output_buffer = [e.copy() for e in self.output_buffer]
+        return c
+
+    def observe_element(self, element):
+        self.output_buffer = []
+        self.input_buffer.append(np.array(element, dtype=np.uint64).reshape(_FIELD_LIMBS[self.ctx.field]))
+
+    def observe_elements(self, elements):
+        for e in elements:
+            self.observe_element(e)
+
+    def observe_affine_point(self, point):
+        """point: (2, L), x then y (the reference asserts it is not the identity)"""
+        self.observe_element(point[0])
+        self.observe_element(point[1])
+
+    def observe_affine_points(self, points):
+        for pt in points:
+            self.observe_affine_point(pt)
+
+    def get_challenge(self):
+        self._absorb_buffered_inputs()
+        if not self.output_buffer:  # plonk_challenger.rs:66-70; never taken, the buffer has just been filled
+            self.sponge_state = rescue_permutation(self.ctx, self.sponge_state)
+            self.output_buffer = [self.sponge_state[i].copy() for i in range(RESCUE_SPONGE_RATE)]
+        return self.output_buffer.pop()
+
+    def get_2_challenges(self):
+        return self.get_challenge(), self.get_challenge()
+
+    def get_3_challenges(self):
+        return self.get_challenge(), self.get_challenge(), self.get_challenge()
+
+    def get_n_challenges(self, n):
+        return [self.get_challenge() for _ in range(n)]
+
+    def _absorb_buffered_inputs(self):
+        for at in range(0, len(self.input_buffer), RESCUE_SPONGE_RATE):
+            chunk = np.stack(self.input_buffer[at:at + RESCUE_SPONGE_RATE])
+            self.sponge_state[:len(chunk)] = field_op(self.ctx.field, "add", self.sponge_state[:len(chunk)], chunk)
+            self.sponge_state = rescue_permutation(self.ctx, self.sponge_state)
+        self.output_buffer = [self.sponge_state[i].copy() for i in range(RESCUE_SPONGE_RATE)]
+        self.input_buffer = []

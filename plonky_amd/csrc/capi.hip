@@ -1623,6 +1623,86 @@ int plk_blake_field(size_t count, int field, const uint8_t* iters, const uint64_
     return PLK_OK;
 }
 
+// ---- Rescue (rescue.hip): count or width first, context / field id second ----
+int plk_rescue_create(size_t width, int field, size_t rounds, const uint64_t* constants, plk_rescue_ctx** out) {
+    PLK_API;
+    return rescue_create_impl(field, width, rounds, constants, out);
+}
+int plk_rescue_free(plk_rescue_ctx* ctx) {
+    PLK_API;
+    return rescue_free_impl(ctx);
+}
+int plk_rescue_rounds(size_t width, size_t security_bits, size_t* rounds) { return rescue_rounds_impl(width, security_bits, rounds); }
+int plk_rescue_mds(size_t width, int field, uint64_t* out) {
+    PLK_API;
+    if (field_limbs(field) < 0) return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
+    if (width != 4) return set_error(PLK_ERR_INVALID_ARG, "width %zu: the Rescue kernels are built for width 4 (RESCUE_SPONGE_WIDTH)", width);
+    if (!out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t bytes = width * width * (size_t)field_limbs(field) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void* dm = nullptr;
+    PLK_TRY(c.tmp(dm, bytes));
+    PLK_TRY(rescue_mds_dev_impl(field, width, dm, c.stream()));
+    PLK_TRY(c.out(out, dm, bytes));
+    return c.finish();
+}
+int plk_rescue_permutation_dev(size_t count, const plk_rescue_ctx* ctx, const void* d_states, void* d_out, void* stream) {
+    PLK_API;
+    return rescue_permutation_dev_impl(count, ctx, d_states, d_out, as_stream(stream));
+}
+int plk_rescue_permutation(size_t count, const plk_rescue_ctx* ctx, const uint64_t* states, uint64_t* out) {
+    PLK_API;
+    PLK_TRY(rescue_check(count, ctx));
+    if (count == 0) return PLK_OK;
+    if (!states || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t bytes = count * 4 * (size_t)field_limbs(rescue_ctx_field(ctx)) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void* ds = nullptr;
+    PLK_TRY(c.in(ds, states, bytes));
+    PLK_TRY(rescue_permutation_dev_impl(count, ctx, ds, ds, c.stream()));
+    PLK_TRY(c.out(out, ds, bytes));
+    return c.finish();
+}
+int plk_rescue_sponge_dev(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const void* d_inputs, size_t n_outputs, void* d_out, void* stream) {
+    PLK_API;
+    return rescue_sponge_dev_impl(count, ctx, n_inputs, d_inputs, n_outputs, d_out, as_stream(stream));
+}
+int plk_rescue_sponge(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const uint64_t* inputs, size_t n_outputs, uint64_t* out) {
+    PLK_API;
+    PLK_TRY(rescue_sponge_check(count, ctx, n_inputs, n_outputs));
+    if (count == 0) return PLK_OK;
+    if ((n_inputs && !inputs) || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t elem = (size_t)field_limbs(rescue_ctx_field(ctx)) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void *di = nullptr, *dout = nullptr;
+    if (n_inputs) PLK_TRY(c.in(di, inputs, count * n_inputs * elem));
+    PLK_TRY(c.tmp(dout, count * n_outputs * elem));
+    PLK_TRY(rescue_sponge_dev_impl(count, ctx, n_inputs, di, n_outputs, dout, c.stream()));
+    PLK_TRY(c.out(out, dout, count * n_outputs * elem));
+    return c.finish();
+}
+int plk_field_kth_root_dev(size_t count, int field, uint32_t k, const void* d_in, void* d_out, void* stream) {
+    PLK_API;
+    return field_kth_root_dev_impl(count, field, k, d_in, d_out, as_stream(stream));
+}
+int plk_field_kth_root(size_t count, int field, uint32_t k, const uint64_t* in, uint64_t* out) {
+    PLK_API;
+    PLK_TRY(field_kth_root_check(count, field, k));
+    if (count == 0) return PLK_OK;
+    if (!in || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t bytes = count * (size_t)field_limbs(field) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void* dx = nullptr;
+    PLK_TRY(c.in(dx, in, bytes));
+    PLK_TRY(field_kth_root_dev_impl(count, field, k, dx, dx, c.stream()));
+    PLK_TRY(c.out(out, dx, bytes));
+    return c.finish();
+}
+
 // ---- scalar side of an IPA round ----
 int plk_field_inner_product_dev(int field, const void* d_a, const void* d_b, size_t count, void* d_out, void* stream) {
     PLK_API;

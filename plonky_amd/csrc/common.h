@@ -179,6 +179,18 @@ int hash_to_curve_dev_impl(int curve, int field_seeds, const void* d_seeds, uint
                            hipStream_t stream);
 int blake_field_check(int field, size_t count);
 int blake_field_dev_impl(int field, const void* d_iters, const void* d_seeds, size_t count, void* d_out_x, void* d_out_y_neg, void* d_status, hipStream_t stream);
+// Rescue (rescue.hip): count first, then the context or the field id; the checks hold the refusals the host entries share
+int rescue_rounds_impl(size_t width, size_t security_bits, size_t* rounds);
+int rescue_mds_dev_impl(int field, size_t width, void* d_out, hipStream_t stream);
+int rescue_create_impl(int field, size_t width, size_t rounds, const uint64_t* constants, plk_rescue_ctx** out);
+int rescue_free_impl(plk_rescue_ctx* ctx);
+int rescue_ctx_field(const plk_rescue_ctx* ctx);
+int rescue_check(size_t count, const plk_rescue_ctx* ctx);
+int rescue_sponge_check(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, size_t n_outputs);
+int rescue_permutation_dev_impl(size_t count, const plk_rescue_ctx* ctx, const void* d_states, void* d_out, hipStream_t stream);
+int rescue_sponge_dev_impl(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const void* d_inputs, size_t n_outputs, void* d_out, hipStream_t stream);
+int field_kth_root_check(size_t count, int field, uint32_t k);
+int field_kth_root_dev_impl(size_t count, int field, uint32_t k, const void* d_in, void* d_out, hipStream_t stream);
 int field_batch_inverse_dev_impl(int field, const void* d_x, void* d_out, void* d_is_zero, unsigned* d_zero_count, size_t count, hipStream_t stream);
 int curve_batch_to_affine_dev_impl(int curve, size_t count, const void* d_xyz, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
 int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* d_constants, const void* d_wires, const void* d_s_sigma, const void* d_z,

@@ -681,3 +681,38 @@ class HaloArgument:
             self.free()
         except Exception:
             pass
+
+
+# ---- Rescue on device-resident tensors (rescue.rs, field.rs:340-375); ctx: api.RescueContext ----
+def rescue_permutation_dev(ctx, states, out=None):
+    """rescue_permutation per state: states (n, 4, L) int64 CUDA tensor, Montgomery form; out may be states itself (in place)."""
+    L = _FIELD_LIMBS[ctx.field]
+    assert states.is_cuda and states.dtype == torch.int64 and states.is_contiguous() and states.shape[1:] == (ctx.width, L)
+    if out is None:
+        out = torch.empty_like(states)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == states.shape
+    _lib.check(_lib.load().plk_rescue_permutation_dev(states.shape[0], ctx.handle, ctypes.c_void_p(states.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def rescue_sponge_dev(ctx, inputs, num_outputs, out=None):
+    """rescue_sponge per row: inputs (n, n_inputs, L) int64 CUDA tensor (n_inputs may be 0) -> (n, num_outputs, L).  One launch."""
+    L = _FIELD_LIMBS[ctx.field]
+    assert inputs.is_cuda and inputs.dtype == torch.int64 and inputs.is_contiguous() and inputs.dim() == 3 and inputs.shape[2] == L
+    n, n_inputs = inputs.shape[0], inputs.shape[1]
+    if out is None:
+        out = torch.empty((n, num_outputs, L), dtype=torch.int64, device=inputs.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (n, num_outputs, L)
+    _lib.check(_lib.load().plk_rescue_sponge_dev(n, ctx.handle, n_inputs, ctypes.c_void_p(inputs.data_ptr()), num_outputs, ctypes.c_void_p(out.data_ptr()),
+                                                 _stream()))
+    return out
+
+
+def kth_root_dev(field, x, k, out=None):
+    """Field::kth_root_u32(k) per element: x (n, L) int64 CUDA tensor; out may be x itself."""
+    assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.shape[-1] == _FIELD_LIMBS[field]
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == x.shape
+    _lib.check(_lib.load().plk_field_kth_root_dev(x.numel() // x.shape[-1], field, int(k), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out

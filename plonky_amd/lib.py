@@ -121,6 +121,17 @@ SYMBOLS = [
     ("plk_hash_field_to_curve", _i, [_sz, _i, _vp, _vp]),
     ("plk_hash_field_to_curve_dev", _i, [_sz, _i, _vp, _vp, _vp]),
     ("plk_blake_field", _i, [_sz, _i, _vp, _vp, _vp, _vp]),
+    # the Rescue entries take the count or the width first (_sz) and the context / field id second
+    ("plk_rescue_create", _i, [_sz, _i, _sz, _vp, _vp]),
+    ("plk_rescue_free", _i, [_vp]),
+    ("plk_rescue_rounds", _i, [_sz, _sz, _vp]),
+    ("plk_rescue_mds", _i, [_sz, _i, _vp]),
+    ("plk_rescue_permutation", _i, [_sz, _vp, _vp, _vp]),
+    ("plk_rescue_permutation_dev", _i, [_sz, _vp, _vp, _vp, _vp]),
+    ("plk_rescue_sponge", _i, [_sz, _vp, _sz, _vp, _sz, _vp]),
+    ("plk_rescue_sponge_dev", _i, [_sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("plk_field_kth_root", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp]),
+    ("plk_field_kth_root_dev", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp, _vp]),
     ("plk_field_inner_product_dev", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("plk_field_fold_slices_dev", _i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("plk_halo_begin_dev", _i, [_i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp]),
