@@ -564,6 +564,33 @@ int plk_field_kth_root_dev(size_t count, int field, uint32_t k, const void* d_in
 int plk_curve_fold_multi_dev(int curve, size_t n_out, unsigned log_inputs, const void* d_g_xy, const void* d_g_zero, const void* d_scalars,
                              void* d_out_xy, void* d_out_zero, void* stream);
 
+/* ---- a point times a scalar of its own, and the Halo endomorphism  (curve_multiplication.rs:5-85, plonk_util.rs:50-110) ---------- */
+/* These entries take the count first and the curve id second (the id-first entries are a pinned set).  Scalars: 4 limbs each,
+ * Montgomery form in the curve's SCALAR field.  Points: affine, 2L limbs each, Montgomery, plus identity flags (p_zero nullable: no
+ * identity among the inputs).  n_scalars and n_points are each `count` or 1: a single element is broadcast over the batch ([s_i] H and
+ * [s] P_i are the common shapes).  Results are the unique affine point, (0, 0) and out_zero = 1 for the identity.  Refused with
+ * PLK_ERR_INVALID_ARG before anything is launched: an unknown curve id, a null required pointer, n_scalars / n_points neither 1 nor
+ * count, count >= 2^32.  count == 0 is PLK_OK and launches nothing.  The _dev forms are asynchronous on `stream` on the calling
+ * thread's device; in place (d_out_xy == d_p_xy) is allowed when n_points == count. */
+/* out_i = [s_i] P_i.  n_scalars and n_points are each `count` or 1 (broadcast).  p_zero / out_zero as elsewhere (p_zero nullable). */
+int plk_curve_scalar_mul(size_t count, int curve, size_t n_scalars, const uint64_t* scalars, size_t n_points,
+                         const uint64_t* p_xy, const uint8_t* p_zero, uint64_t* out_xy, uint8_t* out_zero);
+int plk_curve_scalar_mul_dev(size_t count, int curve, size_t n_scalars, const void* d_scalars, size_t n_points,
+                             const void* d_p_xy, const void* d_p_zero, void* d_out_xy, void* d_out_zero, void* stream);
+/* halo_n (plonk_util.rs:50-75): out_i = n(s_i) = a ZETA_SCALAR + b over the LOW security_bits bits of the canonical s_i, least
+ * significant first, in chunks of two (to_canonical_bool_vec()[..security_bits]); 4 limbs, Montgomery, scalar field.  Curves with the
+ * endomorphism only (BLS12-377: PLK_ERR_INVALID_ARG); security_bits even (the reference's debug_assert), >= 2 and at most the largest
+ * even number <= ScalarField::BITS.  In place is allowed. */
+int plk_halo_n(size_t count, int curve, unsigned security_bits, const uint64_t* scalars, uint64_t* out);
+int plk_halo_n_dev(size_t count, int curve, unsigned security_bits, const void* d_scalars, void* d_out, void* stream);
+/* halo_n_mul (plonk_util.rs:79-110): out_i = [n(s_i)] P_i by Algorithm 1 of the Halo paper - security_bits / 2 steps
+ * Acc = 2 Acc + S with S one of +-P_i, +-phi(P_i), phi(x, y) = (ZETA x, y) - without computing n(s_i).  Same refusals as plk_halo_n
+ * and plk_curve_scalar_mul. */
+int plk_halo_n_mul(size_t count, int curve, unsigned security_bits, size_t n_scalars, const uint64_t* scalars, size_t n_points,
+                   const uint64_t* p_xy, const uint8_t* p_zero, uint64_t* out_xy, uint8_t* out_zero);
+int plk_halo_n_mul_dev(size_t count, int curve, unsigned security_bits, size_t n_scalars, const void* d_scalars, size_t n_points,
+                       const void* d_p_xy, const void* d_p_zero, void* d_out_xy, void* d_out_zero, void* stream);
+
 /* ---- scalar side of an IPA round  (src/halo.rs:63-118) --------------------------------------------------- */
 /* Field::inner_product (field.rs:213-221): *d_out = sum_i a[i] b[i] (one element, device memory).  Asynchronous on `stream`.
  * The point side of a round is plk_msm (msm_parallel on fresh generators: L_j, R_j, halo.rs:87-93) and
@@ -599,7 +626,8 @@ int plk_halo_begin_dev(int curve, size_t n, const void* d_halo_a, const void* d_
  * h_index / u_index / u_prime_scalar (optional: PLK_NO_INDEX, PLK_NO_INDEX, NULL): when the tables were built over
  * [pedersen_g .., pedersen_h, U ..] - the circuit's fixed generators (plonk.rs:46-51) - the positions of pedersen_h and of U in
  * them (both >= n) and the scalar x = halo_n(u_scaling bits) with u_prime = [x] U (halo.rs:46-47, 4 limbs, Montgomery, scalar
- * field; the CALLER vouches for that relation).  [l_j] H + [<a, b>] U' then are two more scalars of the same MSM; without them
+ * field; the CALLER vouches for that relation - both sides come from the library: u_prime = plk_halo_n_mul(u_scaling, U),
+ * u_prime_scalar = plk_halo_n(u_scaling), same security_bits).  [l_j] H + [<a, b>] U' then are two more scalars of the same MSM; without them
  * they are computed beside it (one lane each, ~1 ms, mostly hidden). */
 #define PLK_NO_INDEX ((size_t)-1)
 int plk_halo_begin_tabled_dev(int curve, size_t n, const void* d_halo_a, const void* d_halo_b, const void* d_halo_g_xy, const void* d_halo_g_zero,

@@ -1133,3 +1133,120 @@ class Challenger:
             self.sponge_state = rescue_permutation(self.ctx, self.sponge_state)
         self.output_buffer = [self.sponge_state[i].copy() for i in range(RESCUE_SPONGE_RATE)]
         self.input_buffer = []
+
+
+# ---- a point times a scalar of its own, the Halo endomorphism and the group side of the verifier ----
+# (curve_multiplication.rs:5-85, plonk_util.rs:50-110 / 329-339, halo.rs:157-223, verifier.rs:173-186)
+def _scalar_mul_args(curve, scalars, points, zero):
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    p = _points(curve, points)
+    z = None if zero is None else np.ascontiguousarray(zero, dtype=np.uint8).reshape(-1)
+    assert z is None or z.shape[0] == p.shape[0]
+    count = max(s.shape[0], p.shape[0])
+    return s, p, z, count, np.zeros((count, 2, _CURVE_LIMBS[curve]), dtype=np.uint64), np.zeros(count, dtype=np.uint8)
+
+
+def curve_scalar_mul(curve, scalars, points, zero=None):
+    """CurveScalar * ProjectivePoint per element: out_i = [s_i] P_i.  scalars (n, 4) or (4,) Montgomery limbs in the curve's scalar
+    field, points (n, 2, L) or (2, L) affine; a single scalar or a single point is broadcast.  Returns (points (n, 2, L), zero flags)."""
+    s, p, z, count, out, oz = _scalar_mul_args(curve, scalars, points, zero)
+    _refused(_lib.load().plk_curve_scalar_mul(count, curve, s.shape[0], _ptr(s), p.shape[0], _ptr(p), _ptr(z) if z is not None else None,
+                                              _ptr(out), _ptr(oz)))
+    return out, oz
+
+
+def halo_n(curve, scalars, security_bits=128):
+    """halo_n (plonk_util.rs:50-75) of to_canonical_bool_vec()[..security_bits] per scalar: (n, 4) Montgomery limbs, scalar field."""
+    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    out = np.empty_like(s)
+    _refused(_lib.load().plk_halo_n(s.shape[0], curve, int(security_bits), _ptr(s), _ptr(out)))
+    return out
+
+
+def halo_n_mul(curve, scalars, points, zero=None, security_bits=128):
+    """halo_n_mul (plonk_util.rs:79-110) per element: [n(s_i)] P_i by Algorithm 1; shapes and broadcast as curve_scalar_mul."""
+    s, p, z, count, out, oz = _scalar_mul_args(curve, scalars, points, zero)
+    _refused(_lib.load().plk_halo_n_mul(count, curve, int(security_bits), s.shape[0], _ptr(s), p.shape[0], _ptr(p),
+                                        _ptr(z) if z is not None else None, _ptr(out), _ptr(oz)))
+    return out, oz
+
+
+def halo_g(field, x, us):
+    """halo_g (plonk_util.rs:329-339): g(x, us) = prod over us REVERSED of (u_i x^(2^j) + u_i^-1).  log n products: host-driven."""
+    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    product = powers(field, x, 1)[0:1]  # ONE
+    x_power = np.ascontiguousarray(x, dtype=np.uint64).reshape(1, 4)
+    for i in range(u.shape[0] - 1, -1, -1):
+        u_i = u[i:i + 1]
+        term = field_op(field, "add", field_op(field, "mul", u_i, x_power), field_op(field, "inverse", u_i))
+        product = field_op(field, "mul", product, term)
+        x_power = field_op(field, "square", x_power)
+    return product[0]
+
+
+def _point(curve, p):
+    """a point argument: (2, L) limbs, or (limbs, zero flag)"""
+    if isinstance(p, tuple):
+        return _points(curve, p[0])[0], int(np.asarray(p[1]).reshape(-1)[0])
+    return _points(curve, p)[0], 0
+
+
+def _point_sum(curve, pts):
+    return curve_sum_affine(curve, np.stack([p[0] for p in pts]), np.array([p[1] for p in pts], dtype=np.uint8))
+
+
+def schnorr_protocol(curve, halo_a, halo_b, halo_g, randomness, u_prime, pedersen_h, d, s, challenge):
+    """schnorr_protocol (halo.rs:157-182) with the nonces d, s and the challenge as arguments: R = [d](G + [b] U') + [s] H,
+    z1 = a c + d, z2 = randomness c + s.  Returns ((R limbs, zero flag), z1, z2)."""
+    sf = int(_lib.load().plk_curve_scalar_field(curve))
+    g, up, h = _point(curve, halo_g), _point(curve, u_prime), _point(curve, pedersen_h)
+    bu, buz = curve_scalar_mul(curve, halo_b, up[0], [up[1]])
+    gu = _point_sum(curve, [g, (bu[0], int(buz[0]))])
+    m, mz = curve_scalar_mul(curve, np.stack([np.asarray(d, dtype=np.uint64).reshape(4), np.asarray(s, dtype=np.uint64).reshape(4)]),
+                             np.stack([gu[0], h[0]]), [gu[1], h[1]])
+    r = _point_sum(curve, [(m[0], int(mz[0])), (m[1], int(mz[1]))])
+    c = np.asarray(challenge, dtype=np.uint64).reshape(1, 4)
+    z1 = field_op(sf, "add", field_op(sf, "mul", np.asarray(halo_a, dtype=np.uint64).reshape(1, 4), c), np.asarray(d, dtype=np.uint64).reshape(1, 4))[0]
+    z2 = field_op(sf, "add", field_op(sf, "mul", np.asarray(randomness, dtype=np.uint64).reshape(1, 4), c), np.asarray(s, dtype=np.uint64).reshape(1, 4))[0]
+    return r, z1, z2
+
+
+def verify_ipa(curve, halo_l, halo_r, halo_g, commitment, value, halo_b, halo_us, u_prime, pedersen_h, schnorr_challenge, schnorr_proof):
+    """verify_ipa (halo.rs:186-223).  halo_l / halo_r: (k, 2, L) affine points (or (points, zero flags)); the other points (2, L) or
+    (limbs, zero flag); scalars (4,) Montgomery limbs; schnorr_proof = (R, z1, z2).  P' = C + [value] U',
+    Q = <u^2, L> + <u^-2, R> + P', and the check is [c] Q + R == [z1](G + [b] U') + [z2] H on unique affine points."""
+    sf = int(_lib.load().plk_curve_scalar_field(curve))
+    us = np.ascontiguousarray(halo_us, dtype=np.uint64).reshape(-1, 4)
+    lr, lrz = [], []
+    for side in (halo_l, halo_r):
+        pts, flags = side if isinstance(side, tuple) else (side, None)
+        pts = _points(curve, pts)
+        assert pts.shape[0] == us.shape[0], "one L_j and one R_j per challenge"
+        lr.append(pts)
+        lrz.append(np.zeros(pts.shape[0], dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8).reshape(-1))
+    g, com, up, h = _point(curve, halo_g), _point(curve, commitment), _point(curve, u_prime), _point(curve, pedersen_h)
+    r, z1, z2 = schnorr_proof
+    r = _point(curve, r)
+    one = lambda v: np.asarray(v, dtype=np.uint64).reshape(4)
+    # [value] U' and [b] U': one call, two scalars over the one point
+    t, tz = curve_scalar_mul(curve, np.stack([one(value), one(halo_b)]), up[0], [up[1]])
+    p_prime = _point_sum(curve, [com, (t[0], int(tz[0]))])
+    scalars = np.concatenate([field_op(sf, "square", us), field_op(sf, "square", field_op(sf, "inverse", us))])
+    q = msm_parallel(curve, scalars, np.concatenate(lr), 8, zero=np.concatenate(lrz))
+    q = _point_sum(curve, [q, p_prime])
+    gu = _point_sum(curve, [g, (t[1], int(tz[1]))])
+    m, mz = curve_scalar_mul(curve, np.stack([one(schnorr_challenge), one(z1), one(z2)]), np.stack([q[0], gu[0], h[0]]), [q[1], gu[1], h[1]])
+    lhs = _point_sum(curve, [(m[0], int(mz[0])), r])
+    rhs = _point_sum(curve, [(m[1], int(mz[1])), (m[2], int(mz[2]))])
+    return lhs[1] == rhs[1] and bool(np.array_equal(lhs[0], rhs[0]))
+
+
+def verify_halo_g(curve, halo_g, halo_us, precomputation):
+    """The linear-time G check of the verifier (verifier.rs:173-186): halo_g == <halo_s(us), G> over the caller's tables of the
+    2^len(us) generators (an MsmPrecomputation)."""
+    sf = int(_lib.load().plk_curve_scalar_field(curve))
+    s = halo_s(sf, halo_us)
+    assert s.shape[0] == precomputation.n, "2^len(halo_us) generators"
+    got = msm_execute_parallel(precomputation, s)
+    g = _point(curve, halo_g)
+    return got[1] == g[1] and bool(np.array_equal(got[0], g[0]))

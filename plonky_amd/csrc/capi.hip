@@ -1703,6 +1703,67 @@ int plk_field_kth_root(size_t count, int field, uint32_t k, const uint64_t* in, 
     return c.finish();
 }
 
+// ---- a point times a scalar of its own, the Halo endomorphism (scalar_mul.hip): count first, curve id second ----
+int plk_curve_scalar_mul_dev(size_t count, int curve, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy, const void* d_p_zero,
+                             void* d_out_xy, void* d_out_zero, void* stream) {
+    PLK_API;
+    return curve_scalar_mul_dev_impl(count, curve, n_scalars, d_scalars, n_points, d_p_xy, d_p_zero, d_out_xy, d_out_zero, as_stream(stream));
+}
+int plk_halo_n_dev(size_t count, int curve, unsigned security_bits, const void* d_scalars, void* d_out, void* stream) {
+    PLK_API;
+    return halo_n_dev_impl(count, curve, security_bits, d_scalars, d_out, as_stream(stream));
+}
+int plk_halo_n_mul_dev(size_t count, int curve, unsigned security_bits, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy,
+                       const void* d_p_zero, void* d_out_xy, void* d_out_zero, void* stream) {
+    PLK_API;
+    return halo_n_mul_dev_impl(count, curve, security_bits, n_scalars, d_scalars, n_points, d_p_xy, d_p_zero, d_out_xy, d_out_zero, as_stream(stream));
+}
+// the host-pointer form of the two point entries: security_bits == 0 selects plk_curve_scalar_mul
+static int scalar_mul_host(size_t count, int curve, unsigned security_bits, size_t n_scalars, const uint64_t* scalars, size_t n_points, const uint64_t* p_xy,
+                           const uint8_t* p_zero, uint64_t* out_xy, uint8_t* out_zero) {
+    if (count == 0) return PLK_OK;
+    if (!scalars || !p_xy || !out_xy || !out_zero) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t pt = (size_t)curve_limbs(curve) * 2 * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void *ds = nullptr, *dp = nullptr, *dz = nullptr, *dout = nullptr, *doz = nullptr;
+    PLK_TRY(c.in(ds, scalars, n_scalars * 32));
+    PLK_TRY(c.in(dp, p_xy, n_points * pt));
+    if (p_zero) PLK_TRY(c.in(dz, p_zero, n_points));
+    PLK_TRY(c.tmp(dout, count * pt));
+    PLK_TRY(c.tmp(doz, count));
+    if (security_bits) PLK_TRY(halo_n_mul_dev_impl(count, curve, security_bits, n_scalars, ds, n_points, dp, dz, dout, doz, c.stream()));
+    else PLK_TRY(curve_scalar_mul_dev_impl(count, curve, n_scalars, ds, n_points, dp, dz, dout, doz, c.stream()));
+    PLK_TRY(c.out(out_xy, dout, count * pt));
+    PLK_TRY(c.out(out_zero, doz, count));
+    return c.finish();
+}
+int plk_curve_scalar_mul(size_t count, int curve, size_t n_scalars, const uint64_t* scalars, size_t n_points, const uint64_t* p_xy, const uint8_t* p_zero,
+                         uint64_t* out_xy, uint8_t* out_zero) {
+    PLK_API;
+    PLK_TRY(curve_scalar_mul_check(count, curve, n_scalars, n_points));
+    return scalar_mul_host(count, curve, 0, n_scalars, scalars, n_points, p_xy, p_zero, out_xy, out_zero);
+}
+int plk_halo_n_mul(size_t count, int curve, unsigned security_bits, size_t n_scalars, const uint64_t* scalars, size_t n_points, const uint64_t* p_xy,
+                   const uint8_t* p_zero, uint64_t* out_xy, uint8_t* out_zero) {
+    PLK_API;
+    PLK_TRY(halo_n_mul_check(count, curve, security_bits, n_scalars, n_points));
+    return scalar_mul_host(count, curve, security_bits, n_scalars, scalars, n_points, p_xy, p_zero, out_xy, out_zero);
+}
+int plk_halo_n(size_t count, int curve, unsigned security_bits, const uint64_t* scalars, uint64_t* out) {
+    PLK_API;
+    PLK_TRY(halo_n_check(count, curve, security_bits));
+    if (count == 0) return PLK_OK;
+    if (!scalars || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void* ds = nullptr;
+    PLK_TRY(c.in(ds, scalars, count * 32));
+    PLK_TRY(halo_n_dev_impl(count, curve, security_bits, ds, ds, c.stream()));
+    PLK_TRY(c.out(out, ds, count * 32));
+    return c.finish();
+}
+
 // ---- scalar side of an IPA round ----
 int plk_field_inner_product_dev(int field, const void* d_a, const void* d_b, size_t count, void* d_out, void* stream) {
     PLK_API;

@@ -191,6 +191,16 @@ int rescue_permutation_dev_impl(size_t count, const plk_rescue_ctx* ctx, const v
 int rescue_sponge_dev_impl(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const void* d_inputs, size_t n_outputs, void* d_out, hipStream_t stream);
 int field_kth_root_check(size_t count, int field, uint32_t k);
 int field_kth_root_dev_impl(size_t count, int field, uint32_t k, const void* d_in, void* d_out, hipStream_t stream);
+// a point times a scalar of its own and the Halo endomorphism (scalar_mul.hip): count first, then the curve id; the checks hold the
+// refusals the host entries share
+int curve_scalar_mul_check(size_t count, int curve, size_t n_scalars, size_t n_points);
+int curve_scalar_mul_dev_impl(size_t count, int curve, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy, const void* d_p_zero,
+                              void* d_out_xy, void* d_out_zero, hipStream_t stream);
+int halo_n_check(size_t count, int curve, unsigned security_bits);
+int halo_n_dev_impl(size_t count, int curve, unsigned security_bits, const void* d_scalars, void* d_out, hipStream_t stream);
+int halo_n_mul_check(size_t count, int curve, unsigned security_bits, size_t n_scalars, size_t n_points);
+int halo_n_mul_dev_impl(size_t count, int curve, unsigned security_bits, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy,
+                        const void* d_p_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
 int field_batch_inverse_dev_impl(int field, const void* d_x, void* d_out, void* d_is_zero, unsigned* d_zero_count, size_t count, hipStream_t stream);
 int curve_batch_to_affine_dev_impl(int curve, size_t count, const void* d_xyz, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
 int plonk_vanishing_points_dev_impl(int field, unsigned log_degree, const void* d_constants, const void* d_wires, const void* d_s_sigma, const void* d_z,

@@ -716,3 +716,47 @@ def kth_root_dev(field, x, k, out=None):
     assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == x.shape
     _lib.check(_lib.load().plk_field_kth_root_dev(x.numel() // x.shape[-1], field, int(k), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
     return out
+
+
+# ---- a point times a scalar of its own and the Halo endomorphism on device-resident tensors (scalar_mul.hip) ----
+def _scalar_mul_tensors(curve, scalars, points, zero, out, out_zero):
+    L = _CURVE_LIMBS[curve]
+    ok = lambda t: t.is_cuda and t.is_contiguous()
+    assert ok(scalars) and scalars.dtype == torch.int64 and scalars.shape[-1] == 4
+    assert ok(points) and points.dtype == torch.int64 and points.shape[-2:] == (2, L)
+    ns, npts = scalars.numel() // 4, points.numel() // (2 * L)
+    count = max(ns, npts)
+    assert zero is None or (ok(zero) and zero.dtype == torch.uint8 and zero.numel() == npts)
+    if out is None:
+        out = torch.empty((count, 2, L), dtype=torch.int64, device=points.device)
+    if out_zero is None:
+        out_zero = torch.empty(count, dtype=torch.uint8, device=points.device)
+    assert ok(out) and out.dtype == torch.int64 and out.numel() == count * 2 * L and ok(out_zero) and out_zero.dtype == torch.uint8 and out_zero.numel() == count
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    return count, ns, npts, p(scalars), p(points), p(zero), p(out), p(out_zero), out, out_zero
+
+
+def scalar_mul_dev(curve, scalars, points, zero=None, out=None, out_zero=None):
+    """out_i = [s_i] P_i: scalars (n, 4) or (1, 4), points (n, 2, L) or (1, 2, L) int64 CUDA tensors (Montgomery), zero: uint8 flags of
+    the points or None.  out may be `points` itself when there are n points.  Returns (out, out_zero)."""
+    count, ns, npts, s, p, z, o, oz, out, out_zero = _scalar_mul_tensors(curve, scalars, points, zero, out, out_zero)
+    _lib.check(_lib.load().plk_curve_scalar_mul_dev(count, curve, ns, s, npts, p, z, o, oz, _stream()))
+    return out, out_zero
+
+
+def halo_n_dev(curve, scalars, security_bits=128, out=None):
+    """n(s_i) of the low security_bits bits: scalars (n, 4) int64 CUDA tensor; out may be scalars itself."""
+    assert scalars.is_cuda and scalars.dtype == torch.int64 and scalars.is_contiguous() and scalars.shape[-1] == 4
+    if out is None:
+        out = torch.empty_like(scalars)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == scalars.shape
+    _lib.check(_lib.load().plk_halo_n_dev(scalars.numel() // 4, curve, int(security_bits), ctypes.c_void_p(scalars.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                          _stream()))
+    return out
+
+
+def halo_n_mul_dev(curve, scalars, points, zero=None, security_bits=128, out=None, out_zero=None):
+    """out_i = [n(s_i)] P_i by Algorithm 1; tensors as scalar_mul_dev."""
+    count, ns, npts, s, p, z, o, oz, out, out_zero = _scalar_mul_tensors(curve, scalars, points, zero, out, out_zero)
+    _lib.check(_lib.load().plk_halo_n_mul_dev(count, curve, int(security_bits), ns, s, npts, p, z, o, oz, _stream()))
+    return out, out_zero

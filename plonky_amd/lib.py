@@ -132,6 +132,13 @@ SYMBOLS = [
     ("plk_rescue_sponge_dev", _i, [_sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     ("plk_field_kth_root", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp]),
     ("plk_field_kth_root_dev", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp, _vp]),
+    # the scalar-multiplication entries take the count first (_sz) and the curve id second
+    ("plk_curve_scalar_mul", _i, [_sz, _i, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("plk_curve_scalar_mul_dev", _i, [_sz, _i, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_halo_n", _i, [_sz, _i, _u, _vp, _vp]),
+    ("plk_halo_n_dev", _i, [_sz, _i, _u, _vp, _vp, _vp]),
+    ("plk_halo_n_mul", _i, [_sz, _i, _u, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("plk_halo_n_mul_dev", _i, [_sz, _i, _u, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("plk_field_inner_product_dev", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("plk_field_fold_slices_dev", _i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("plk_halo_begin_dev", _i, [_i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _u, _vp, _vp]),
