@@ -554,6 +554,26 @@ int plk_rescue_sponge_dev(size_t count, const plk_rescue_ctx* ctx, size_t n_inpu
 int plk_field_kth_root(size_t count, int field, uint32_t k, const uint64_t* in, uint64_t* out);
 int plk_field_kth_root_dev(size_t count, int field, uint32_t k, const void* d_in, void* d_out, void* stream);
 
+/* ---- the Rescue hash to the curve  (src/hash_to_curve.rs:3-11, 78-104) ------------------------------------------------------------ */
+/* hash_base_field_to_curve::<C>(seed, security_bits), which plonk_recursion.rs:274,384 derives u and pedersen_h of an inner circuit
+ * with: try i = 0, 1, ... squeezes two outputs from rescue_sponge([seed, from_canonical_u32(i)], 2, security_bits) - one permutation -
+ * x is the first, y_neg bit 0 of the canonical form of the second, and the point is (x, y_neg ? -y : y) with
+ * y = Field::square_root(x^3 + B) for the first i at which the root exists.  security_bits is the context's number of rounds
+ * (plk_rescue_rounds) and the constants are the context's; its field must be the curve's base field and it must live on the calling
+ * thread's device.  plk_rescue_hash_to_curve hashes the integers seed_start + k, k < count, taken through from_canonical_usize
+ * (hash_usize_to_curve; hash_u32_to_curve for seeds below 2^32); plk_rescue_hash_field_to_curve hashes `count` base-field elements,
+ * L limbs each, Montgomery form.  out_xy = count affine points x || y, 2L limbs each, Montgomery form; never the identity.  A seed
+ * with no point after 256 tries (probability 2^-256) gets zero coordinates, and the host-pointer forms return PLK_ERR_INVALID_ARG.
+ * A null context, an unknown curve id, a context of another field or on another device, count >= 2^32 and a null pointer are
+ * PLK_ERR_INVALID_ARG before anything is launched or copied; count == 0 is PLK_OK and launches nothing.  The _dev forms are
+ * asynchronous on `stream` and write device memory that feeds plk_msm_precompute_table_dev and the MSM contexts as it is.  The output
+ * is bit-identical from run to run.  Count first and context second, like every entry added after the pinned id-first set.
+ * PLK_H2C_NAIVE=1 (read once) runs one quad per seed through all its tries instead of rounds over a compacted work list: same bytes. */
+int plk_rescue_hash_to_curve(size_t count, const plk_rescue_ctx* ctx, int curve, uint64_t seed_start, uint64_t* out_xy);
+int plk_rescue_hash_to_curve_dev(size_t count, const plk_rescue_ctx* ctx, int curve, uint64_t seed_start, void* d_out_xy, void* stream);
+int plk_rescue_hash_field_to_curve(size_t count, const plk_rescue_ctx* ctx, int curve, const uint64_t* seeds, uint64_t* out_xy);
+int plk_rescue_hash_field_to_curve_dev(size_t count, const plk_rescue_ctx* ctx, int curve, const void* d_seeds, void* d_out_xy, void* stream);
+
 /* r = log_inputs rounds of that fold at once, in the scaled form halo.hip keeps its generators in:
  *     out_i = g_i + sum_{t = 1 .. 2^r - 1} [s_t] g_{i + t n_out},   i < n_out,
  * g = 2^r n_out affine points (+ optional identity flags), the 2^r scalars in DEVICE memory (4 limbs each, Montgomery, scalar

@@ -1051,6 +1051,34 @@ def rescue_sponge(ctx, inputs, num_outputs):
     return out[0] if single else out
 
 
+# ---- the Rescue hash to the curve (hash_to_curve.rs:3-11, 78-104); ctx: a RescueContext over the curve's base field ----
+def hash_base_field_to_curve(ctx, curve, seeds):
+    """hash_base_field_to_curve::<C>(seed, security_bits) per row of seeds ((n, L) or (L,) Montgomery limbs of the base field), the
+    context's rounds standing for security_bits: (n, 2, L) or (2, L) affine points."""
+    a = np.ascontiguousarray(seeds, dtype=np.uint64)
+    single = a.ndim == 1
+    a = _elems(CURVE_BASE_FIELD[curve], a.reshape(1, -1) if single else a)
+    out = np.empty((a.shape[0], 2, a.shape[1]), dtype=np.uint64)
+    _refused(_lib.load().plk_rescue_hash_field_to_curve(a.shape[0], ctx.handle, curve, _ptr(a), _ptr(out)))
+    return out[0] if single else out
+
+
+def hash_usize_to_curve(ctx, curve, seed, count=None):
+    """hash_usize_to_curve::<C>(seed, security_bits): (2, L); with count, the points of seed .. seed + count - 1: (count, 2, L)."""
+    n = 1 if count is None else int(count)
+    out = np.empty((n, 2, _CURVE_LIMBS.get(curve, 4)), dtype=np.uint64)
+    _refused(_lib.load().plk_rescue_hash_to_curve(n, ctx.handle, curve, int(seed), _ptr(out)))
+    return out[0] if count is None else out
+
+
+def hash_u32_to_curve(ctx, curve, seed, count=None):
+    """hash_u32_to_curve::<C>(seed, security_bits): hash_usize_to_curve over seeds that fit a u32."""
+    last = int(seed) + (1 if count is None else int(count)) - 1
+    if int(seed) < 0 or last >= 1 << 32:
+        raise ValueError("seeds %d .. %d do not fit a u32" % (int(seed), last))
+    return hash_usize_to_curve(ctx, curve, seed, count)
+
+
 def rescue_hash_n_to_1(ctx, inputs):  # rescue.rs:26-28
     return rescue_sponge(ctx, inputs, 1)
 

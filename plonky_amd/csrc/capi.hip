@@ -1703,6 +1703,47 @@ int plk_field_kth_root(size_t count, int field, uint32_t k, const uint64_t* in, 
     return c.finish();
 }
 
+// ---- the Rescue hash to the curve (rescue_h2c.hip): count first, context second ----
+int plk_rescue_hash_to_curve_dev(size_t count, const plk_rescue_ctx* ctx, int curve, uint64_t seed_start, void* d_out_xy, void* stream) {
+    PLK_API;
+    return rescue_h2c_dev_impl(count, ctx, curve, 0, nullptr, seed_start, d_out_xy, nullptr, as_stream(stream));
+}
+int plk_rescue_hash_field_to_curve_dev(size_t count, const plk_rescue_ctx* ctx, int curve, const void* d_seeds, void* d_out_xy, void* stream) {
+    PLK_API;
+    return rescue_h2c_dev_impl(count, ctx, curve, 1, d_seeds, 0, d_out_xy, nullptr, as_stream(stream));
+}
+// the host-pointer forms: seeds == nullptr is the integer form
+static int rescue_h2c_host(size_t count, const plk_rescue_ctx* ctx, int curve, const uint64_t* seeds, int field_seeds, uint64_t seed_start, uint64_t* out_xy) {
+    PLK_TRY(rescue_h2c_check(count, ctx, curve));
+    if (count == 0) return PLK_OK;
+    if (!out_xy || (field_seeds && !seeds)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    const size_t coord = (size_t)curve_limbs(curve) * 8;
+    LaneCall c;
+    PLK_TRY(c.begin());
+    c.pin(seeds, count * coord);
+    c.pin(out_xy, count * 2 * coord);
+    void *dseeds = nullptr, *dp = nullptr, *ds = nullptr;
+    if (field_seeds) PLK_TRY(c.in(dseeds, seeds, count * coord));
+    PLK_TRY(c.tmp(dp, count * 2 * coord));
+    PLK_TRY(c.tmp(ds, count));
+    PLK_TRY(rescue_h2c_dev_impl(count, ctx, curve, field_seeds, dseeds, seed_start, dp, ds, c.stream()));
+    std::vector<uint8_t> st(count);
+    PLK_TRY(c.out(st.data(), ds, count));
+    PLK_TRY(c.out(out_xy, dp, count * 2 * coord));
+    PLK_TRY(c.finish());
+    for (size_t k = 0; k < count; ++k)
+        if (st[k]) return set_error(PLK_ERR_INVALID_ARG, "seed %zu has no point: i passed 255 (hash_to_curve.rs:84)", k);
+    return PLK_OK;
+}
+int plk_rescue_hash_to_curve(size_t count, const plk_rescue_ctx* ctx, int curve, uint64_t seed_start, uint64_t* out_xy) {
+    PLK_API;
+    return rescue_h2c_host(count, ctx, curve, nullptr, 0, seed_start, out_xy);
+}
+int plk_rescue_hash_field_to_curve(size_t count, const plk_rescue_ctx* ctx, int curve, const uint64_t* seeds, uint64_t* out_xy) {
+    PLK_API;
+    return rescue_h2c_host(count, ctx, curve, seeds, 1, 0, out_xy);
+}
+
 // ---- a point times a scalar of its own, the Halo endomorphism (scalar_mul.hip): count first, curve id second ----
 int plk_curve_scalar_mul_dev(size_t count, int curve, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy, const void* d_p_zero,
                              void* d_out_xy, void* d_out_zero, void* stream) {

@@ -189,6 +189,10 @@ int rescue_check(size_t count, const plk_rescue_ctx* ctx);
 int rescue_sponge_check(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, size_t n_outputs);
 int rescue_permutation_dev_impl(size_t count, const plk_rescue_ctx* ctx, const void* d_states, void* d_out, hipStream_t stream);
 int rescue_sponge_dev_impl(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs, const void* d_inputs, size_t n_outputs, void* d_out, hipStream_t stream);
+// the Rescue hash to the curve (rescue_h2c.hip): count first, context second; the check holds the refusals the host entries share
+int rescue_h2c_check(size_t count, const plk_rescue_ctx* ctx, int curve);
+int rescue_h2c_dev_impl(size_t count, const plk_rescue_ctx* ctx, int curve, int field_seeds, const void* d_seeds, uint64_t seed_start, void* d_out_xy,
+                        void* d_status, hipStream_t stream);
 int field_kth_root_check(size_t count, int field, uint32_t k);
 int field_kth_root_dev_impl(size_t count, int field, uint32_t k, const void* d_in, void* d_out, hipStream_t stream);
 // a point times a scalar of its own and the Halo endomorphism (scalar_mul.hip): count first, then the curve id; the checks hold the

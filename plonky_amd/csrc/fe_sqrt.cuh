@@ -1,5 +1,6 @@
 // fe_sqrt.cuh -- Field::square_root (field.rs:440-472) on the arithmetic of fp.cuh, shared by the point decompression (serial.hip)
-// and the hash to the curve (hash_to_curve.hip).  Device code.
+// and the two hashes to the curve (hash_to_curve.hip, rescue_h2c.hip).  Device code; fe_sqrt_with also serves the host replay of
+// rescue_h2c_step.cuh.
 #pragma once
 #include "fp.cuh"
 #include "tables.cuh"
@@ -31,10 +32,12 @@ template <class P> struct SqrtRootBySquaring {  // the reference's way: j squari
         return w;
     }
 };
+#ifdef __HIPCC__
 template <class P> struct SqrtRootFromTable {  // tab[m] = ROOT_2ADIC^(2^m), m < TWO_ADICITY, as fe_store leaves them
     const uint4* tab;
     PLK_DI Fe<P> operator()(const Fe<P>& /*z*/, int /*j*/, int m) const { return fe_load<P>(tab + (size_t)m * (P::NL / 4)); }
 };
+#endif
 
 // Tonelli-Shanks with z = g^T, T = (p - 1) / 2^TWO_ADICITY.  Returns false for a non-residue (the reference tests Euler's
 // criterion first; here the same fact falls out of the loop: b = a^T has order dividing 2^(adicity - 1) exactly when a is a square).
@@ -80,9 +83,21 @@ template <class P, class RootPow> PLK_DI bool fe_sqrt_with(const Fe<P>& a, Fe<P>
     return true;
 }
 template <class P> PLK_DNI bool fe_sqrt(const Fe<P>& a, Fe<P>& root) { return fe_sqrt_with<P>(a, root, SqrtRootBySquaring<P>{}); }
-// the same root with the table of powers in place of the squarings (hash_to_curve.hip builds the table)
+#ifdef __HIPCC__
+// the same root with the table of powers in place of the squarings (k_h2c_root_table below builds the table)
 template <class P> PLK_DNI bool fe_sqrt_tabled(const Fe<P>& a, Fe<P>& root, const uint4* tab) {
     return fe_sqrt_with<P>(a, root, SqrtRootFromTable<P>{tab});
 }
+
+// tab[m] = ROOT_2ADIC^(2^m), m < TWO_ADICITY: the w of every Tonelli-Shanks step, for fe_sqrt_tabled (one lane, once per call)
+template <class P> __global__ void k_h2c_root_table(uint4* __restrict__ tab) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Fe<P> w = fe_const<P>(P::ROOT_2ADIC);
+    for (int m = 0; m < P::TWO_ADICITY; ++m) {
+        fe_store<P>(tab + (size_t)m * (P::NL / 4), w);
+        w = fe_sqr<P>(w);
+    }
+}
+#endif
 
 }  // namespace plk

@@ -7,6 +7,7 @@
 // counter 0, block_len = the message length, flags CHUNK_START | CHUNK_END | ROOT, and the 16 output words are the first 64 bytes
 // of the extended output.  No tree, no chunk counter, no multi-block path.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "field_params.cuh"
@@ -64,6 +65,13 @@ H2C_HD void h2c_blake3_block(const uint32_t (&msg)[16], uint32_t len, uint32_t (
         out[k] = v[k] ^ v[k + 8];
         out[k + 8] = v[k + 8] ^ iv[k];
     }
+}
+
+// bit_length(count) + 2 rounds over the work list of either hash to the curve: the expected number of seeds open afterwards is below one
+inline int h2c_rounds(size_t count) {
+    int bits = 0;
+    for (size_t c = count; c; c >>= 1) ++bits;
+    return bits + 2 < H2C_TRIES ? bits + 2 : H2C_TRIES;
 }
 
 // is_valid_canonical: the value is below the modulus

@@ -24,16 +24,6 @@ namespace plk {
 
 constexpr int H2C_LANES = 64;  // one wave per workgroup: the compaction is wave-wide, and short lists spread over the CUs
 
-// tab[m] = ROOT_2ADIC^(2^m), m < TWO_ADICITY: the w of every Tonelli-Shanks step (fe_sqrt.cuh)
-template <class P> __global__ void k_h2c_root_table(uint4* __restrict__ tab) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    Fe<P> w = fe_const<P>(P::ROOT_2ADIC);
-    for (int m = 0; m < P::TWO_ADICITY; ++m) {
-        fe_store<P>(tab + (size_t)m * (P::NL / 4), w);
-        w = fe_sqr<P>(w);
-    }
-}
-
 template <class P> PLK_DI Fe<P> h2c_words_to_fe(const uint32_t (&w)[P::NL]) {
     Fe<P> r;
 #pragma unroll
@@ -115,12 +105,6 @@ __global__ void __launch_bounds__(H2C_LANES) k_h2c_tries(const uint4* __restrict
         const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
         if (at < count) next[at] = k;  // at most `open` <= count seeds stay open
     }
-}
-
-static int h2c_rounds(size_t count) {  // bit_length(count) + 2: the expected number of seeds open afterwards is below one
-    int bits = 0;
-    for (size_t c = count; c; c >>= 1) ++bits;
-    return bits + 2 < H2C_TRIES ? bits + 2 : H2C_TRIES;
 }
 
 template <class C>

@@ -13,33 +13,13 @@
 // steer scalar branches.  For its row a lane fetches the three other elements from its neighbours with DPP quad broadcasts
 // (ecz_coop.cuh) and forms the four products under one reduction.  A state stays in the registers of its four lanes from the load to
 // the store; the sponge's absorb and squeeze loops run inside the kernel, so a call is one launch however many permutations it holds.
-#include "common.h"
-#include "ecz_coop.cuh"
-#include "rescue_step.cuh"
-
-struct plk_rescue_ctx {
-    int field = -1;
-    int device = -1;         // the physical device the tables live on
-    size_t width = 0, rounds = 0;
-    int windows = 0;         // 4-bit digits of the exponent of 1 / alpha
-    void* d_buf = nullptr;   // mds | constants | exponent | (the constants as they came: read by the setup kernel only)
-    const uint32_t* d_mds = nullptr;
-    const uint32_t* d_consts = nullptr;
-    const uint32_t* d_exp = nullptr;
-};
+#include "rescue_lane.cuh"
 
 namespace plk {
 
 constexpr int RESCUE_LANES = 256;                          // 64 states per workgroup
 constexpr int RESCUE_STATES = RESCUE_LANES / RESCUE_WIDTH;
 
-struct RescueTables {
-    const uint32_t* mds;     // W x W entries, row-major, table form (rescue_step.cuh)
-    const uint32_t* consts;  // rounds x 2 x W constants, step A then step B per round, table form
-    const uint32_t* exp;     // NL words: the exponent of 1 / alpha
-    int windows;
-    uint32_t rounds;
-};
 struct RescueExponent {  // the exponent of a k-th root as a kernel argument
     uint32_t w[12];
     int windows;
@@ -63,25 +43,6 @@ __global__ void __launch_bounds__(64) k_rescue_setup(const uint4* __restrict__ c
             for (int l = 0; l < NZ; ++l) mds_tab[(size_t)e * NZ + l] = v.l[l];
         }
     }
-}
-
-// row e of the matrix over the quad's four elements (y: this lane's), plus the constant
-template <class P> PLK_DI Fz<P> rescue_lane_row(const Fz<P>& y, const uint32_t* __restrict__ mrow, const uint32_t* __restrict__ k) {
-    const Fz<P> x[RESCUE_WIDTH] = {quad_bcast<P, 0>(y), quad_bcast<P, 1>(y), quad_bcast<P, 2>(y), quad_bcast<P, 3>(y)};
-    return rescue_mds_row<P>(x, mrow, k);
-}
-
-// the permutation of the quad's state; x: element e of it, lazy R'-form
-template <class P> PLK_DI Fz<P> rescue_lane_permute(Fz<P> x, const RescueTables& t, int e) {
-    constexpr int NZ = FzCfg<P>::NZ;
-    const uint32_t* mrow = t.mds + e * RESCUE_WIDTH * NZ;
-#pragma unroll 1
-    for (uint32_t r = 0; r < t.rounds; ++r) {
-        const uint32_t* k = t.consts + ((size_t)r * 2 * RESCUE_WIDTH + e) * NZ;
-        x = rescue_lane_row<P>(rescue_pow<P>(x, t.exp, t.windows), mrow, k);
-        x = rescue_lane_row<P>(rescue_pow_alpha<P>(x), mrow, k + RESCUE_WIDTH * NZ);
-    }
-    return x;
 }
 
 template <class P>
@@ -230,14 +191,6 @@ int rescue_sponge_check(size_t count, const plk_rescue_ctx* ctx, size_t n_inputs
     return PLK_OK;
 }
 
-static int rescue_on_ctx_device(const plk_rescue_ctx* ctx) {
-    PLK_TRY(ensure_device());
-    int dev = -1;
-    PLK_HIP_TRY(hipGetDevice(&dev));
-    if (dev != ctx->device) return set_error(PLK_ERR_INVALID_ARG, "the context lives on device %d, the calling thread works on device %d", ctx->device, dev);
-    return PLK_OK;
-}
-static RescueTables rescue_tables(const plk_rescue_ctx* ctx) { return RescueTables{ctx->d_mds, ctx->d_consts, ctx->d_exp, ctx->windows, (uint32_t)ctx->rounds}; }
 static unsigned rescue_blocks(size_t count) { return (unsigned)((count + RESCUE_STATES - 1) / RESCUE_STATES); }
 
 int rescue_permutation_dev_impl(size_t count, const plk_rescue_ctx* ctx, const void* d_states, void* d_out, hipStream_t stream) {

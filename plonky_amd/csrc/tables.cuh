@@ -12,6 +12,7 @@ template <class P> PLK_DI Fe<P> to_rprime(const Fe<P>& v) {
     return fz_to_fe_canonical<P>(fz_mul<P>(fz_from_fe<P>(v), fz_const_r_to_rprime<P>()));
 }
 
+#ifdef __HIPCC__
 // prod_b pw[base_off + b]^(bit b of e), b < log_t: a power of w from its table of repeated squares (R-form)
 template <class P> PLK_DI Fe<P> pow_from_table(const uint4* pw, int base_off, uint64_t e, int log_t) {
     Fe<P> r = fe_one<P>();
@@ -19,6 +20,7 @@ template <class P> PLK_DI Fe<P> pow_from_table(const uint4* pw, int base_off, ui
         if ((e >> b) & 1) r = fe_mul<P>(r, fe_load<P>(pw + (base_off + b) * (P::NL / 4)));
     return r;
 }
+#endif
 
 // x^e by square-and-multiply, R-form
 template <class P> PLK_DI Fe<P> fe_pow_u64(Fe<P> x, uint64_t e) {
@@ -51,6 +53,7 @@ struct PlkWords3 {  // 12 bytes, word-aligned (a 3-vector type would be padded t
     uint32_t x, y, z;
 };
 static_assert(sizeof(PlkWords3) == 12 && alignof(PlkWords3) == 4, "three packed words");
+#ifdef __HIPCC__  // uint4 movement; the rest of this file is plain C++ (fe_sqrt.cuh brings it into a host replay)
 template <class P> PLK_DI Fz<P> limbs_load(const uint32_t* __restrict__ base, size_t e) {
     constexpr int NZ = FzCfg<P>::NZ;
     Fz<P> r;
@@ -95,6 +98,7 @@ template <class P> PLK_DI void limbs_store(uint32_t* __restrict__ base, size_t e
         for (int i = 0; i < U; ++i) p[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
     }
 }
+#endif
 constexpr size_t limb_bytes(size_t elems, int nz) { return elems * (size_t)limb_words(nz) * 4; }
 
 template <class P> PLK_DI Fe<P> fe_const(const uint32_t (&c)[P::NL]) {

@@ -708,6 +708,37 @@ def rescue_sponge_dev(ctx, inputs, num_outputs, out=None):
     return out
 
 
+def _rescue_h2c_call(rc):
+    if rc == _lib.PLK_ERR_INVALID_ARG:
+        raise ValueError(_lib.load().plk_last_error().decode())
+    _lib.check(rc)
+
+
+def rescue_hash_to_curve_dev(ctx, curve, count, seed_start=0, out=None, device="cuda"):
+    """hash_usize_to_curve (hash_to_curve.rs:8-11, 78-104) of the integers seed_start .. seed_start + count - 1 on the device; ctx: an
+    api.RescueContext over the curve's base field, its rounds standing for security_bits.  (count, 2, L) int64 tensor that
+    msm_precompute_dev takes as it is."""
+    L = _CURVE_LIMBS[curve]
+    if out is None:
+        out = torch.empty((count, 2, L), dtype=torch.int64, device=device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
+    _rescue_h2c_call(_lib.load().plk_rescue_hash_to_curve_dev(count, ctx.handle, curve, int(seed_start), ctypes.c_void_p(out.data_ptr()), _stream()))
+    return out
+
+
+def rescue_hash_field_to_curve_dev(ctx, curve, seeds, out=None):
+    """hash_base_field_to_curve per row: seeds (count, L) int64 CUDA tensor, Montgomery form -> (count, 2, L)."""
+    L = _CURVE_LIMBS[curve]
+    assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.dim() == 2 and seeds.shape[1] == L
+    count = seeds.shape[0]
+    if out is None:
+        out = torch.empty((count, 2, L), dtype=torch.int64, device=seeds.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
+    _rescue_h2c_call(_lib.load().plk_rescue_hash_field_to_curve_dev(count, ctx.handle, curve, ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                                  _stream()))
+    return out
+
+
 def kth_root_dev(field, x, k, out=None):
     """Field::kth_root_u32(k) per element: x (n, L) int64 CUDA tensor; out may be x itself."""
     assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.shape[-1] == _FIELD_LIMBS[field]

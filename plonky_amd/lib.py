@@ -132,6 +132,11 @@ SYMBOLS = [
     ("plk_rescue_sponge_dev", _i, [_sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     ("plk_field_kth_root", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp]),
     ("plk_field_kth_root_dev", _i, [_sz, _i, ctypes.c_uint32, _vp, _vp, _vp]),
+    # the Rescue hash to the curve: the count first (_sz), the context second, then the curve id
+    ("plk_rescue_hash_to_curve", _i, [_sz, _vp, _i, _u64, _vp]),
+    ("plk_rescue_hash_to_curve_dev", _i, [_sz, _vp, _i, _u64, _vp, _vp]),
+    ("plk_rescue_hash_field_to_curve", _i, [_sz, _vp, _i, _vp, _vp]),
+    ("plk_rescue_hash_field_to_curve_dev", _i, [_sz, _vp, _i, _vp, _vp, _vp]),
     # the scalar-multiplication entries take the count first (_sz) and the curve id second
     ("plk_curve_scalar_mul", _i, [_sz, _i, _sz, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("plk_curve_scalar_mul_dev", _i, [_sz, _i, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
