@@ -131,7 +131,11 @@ int plk_ntt_precompute_table_dev(int field, unsigned log_n, void* d_out, void* s
  * ifft_with_precomputation_power_of_2 (fft.rs:82-101) when inverse != 0.
  * in/out: 2^log_n elements, natural order in, natural order out; in == out allowed. */
 int plk_ntt(int field, unsigned log_n, int inverse, const uint64_t* in, uint64_t* out);
-/* `batch` independent transforms (the 9 wire polynomials, src/plonk_util.rs:169-190). */
+/* `batch` independent transforms (the 9 wire polynomials, src/plonk_util.rs:169-190).
+ * Host-pointer aliasing, here and in plk_ntt_padded_batch / plk_msm_execute_batch: the inputs (scalar vectors) may overlap each
+ * other, may be the same buffer in several slots, and may be shared with calls of other threads running at the same time;
+ * out[b] == in[b] is allowed (in place); an output that overlaps another output or a DIFFERENT slot's input is not.  Any
+ * alignment, any readable / writable host memory, also memory the caller has registered with the runtime. */
 int plk_ntt_batch(int field, unsigned log_n, int inverse, unsigned batch, const uint64_t* const* in, uint64_t* const* out);
 /* Same on device-resident data: `batch` transforms stored back to back (batch * 2^log_n elements).
  * d_in == d_out allowed.  Asynchronous on `stream`. */
@@ -140,6 +144,7 @@ int plk_ntt_dev(int field, unsigned log_n, int inverse, unsigned batch, const vo
 int plk_ntt_padded(int field, unsigned log_n, const uint64_t* in, size_t n_in, uint64_t* out);
 /* polynomials_to_values_padded (plonk_util.rs:179-190) / Polynomial::eval_domain (polynomial.rs:135-143):
  * `batch` polynomials of n_in[b] <= 2^log_n coefficients each, zero-padded to the domain and transformed.
+ * Aliasing as for plk_ntt_batch: out[b] == in[b] is allowed although the output is longer than the input.
  * The padding is never materialised: the first pass reads only the stored coefficients. */
 int plk_ntt_padded_batch(int field, unsigned log_n, unsigned batch, const uint64_t* const* in, const size_t* n_in, uint64_t* const* out);
 /* Device form: polynomial b starts at d_in + b * in_stride elements and has in_len coefficients; outputs are
@@ -394,6 +399,7 @@ unsigned plk_msm_ctx_window(const plk_msm_ctx* ctx);  /* window size c actually 
  * out_xy: 2L limbs, out_zero: 1 byte. */
 int plk_msm_execute(plk_msm_ctx* ctx, const uint64_t* scalars, size_t n_scalars, uint64_t* out_xy, uint8_t* out_zero);
 /* `batch` scalar vectors against the same generators (commit_polynomials, src/plonk_util.rs:215-231).
+ * Aliasing as for plk_ntt_batch: the vectors may overlap, repeat, and be shared between threads; out_xy / out_zero overlap none.
  * scalars[b]: n limbs*4 each; out_xy: batch * 2L limbs; out_zero: batch bytes. */
 int plk_msm_execute_batch(plk_msm_ctx* ctx, unsigned batch, const uint64_t* const* scalars, size_t n_scalars, uint64_t* out_xy,
                           uint8_t* out_zero);

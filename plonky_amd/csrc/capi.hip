@@ -15,6 +15,7 @@
 #include "common.h"
 #include "ec.cuh"
 #include "host_lane.h"
+#include "pin_registry.h"
 
 struct plk_msm_ctx;
 struct plk_halo_ctx;
@@ -237,136 +238,36 @@ int lane_get(HostLane*& out) {
     return PLK_OK;
 }
 
-// Registered caller ranges: NON-OVERLAPPING intervals, each with the threads that hold it (host_lane.h).  A request inside a
-// registered interval shares it; a request that extends or partly overlaps one never leaves a half-registered range behind (HIP
-// resolves a pointer to the registered object it starts in - an asynchronous copy longer than that object is rejected, and the
-// first holder's release would unregister pages under the second caller's DMA):
-//  * held by OTHER threads: wait until they have released it, then register the union - for at most two seconds in all: holders that
-//    in turn wait for this thread (or for a lock its dispatcher holds) would otherwise never release; past that the request fails and
-//    the caller's copies go without a registration;
-//  * held by the calling thread alone (two overlapping buffers of one batched call, an in-place padded transform): every device
-//    of the group is synchronised - the thread's own copies over the old interval are complete - and the interval is re-registered
-//    as the union, the thread's holds carried over.
-struct PinEntry {
-    size_t bytes;
-    std::map<std::thread::id, unsigned> holders;
-    unsigned refs() const {
-        unsigned r = 0;
-        for (const auto& h : holders) r += h.second;
-        return r;
+// The caller-buffer registry (pin_registry.h has the rules and the code; host_lane.h the callers): here only its three outside
+// effects - hipHostRegister as portable (every device of the group may copy from the range), hipHostUnregister, and "every device
+// of the group quiet" - and the library's one instance, with the two-second wait limit.
+struct HipPinPolicy {
+    bool register_range(const uint8_t* lo, size_t bytes) {
+        if (hipHostRegister(const_cast<uint8_t*>(lo), bytes, hipHostRegisterPortable) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    }
+    void unregister_range(const uint8_t* lo) { (void)hipHostUnregister(const_cast<uint8_t*>(lo)); }
+    void quiesce() {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        for (int d = 0; d < group_size(); ++d) {
+            if (d && group_phys(d) == group_phys(d - 1)) continue;
+            (void)hipSetDevice(group_phys(d));
+            (void)hipDeviceSynchronize();
+        }
+        if (cur >= 0) (void)hipSetDevice(cur);
     }
 };
-static std::mutex g_pin_mu;
-static std::condition_variable g_pin_cv;
-static std::map<const uint8_t*, PinEntry> g_pins;  // by start address; intervals never overlap
+static PinRegistry<HipPinPolicy>& pin_registry() {
+    static PinRegistry<HipPinPolicy>* r = new PinRegistry<HipPinPolicy>(2000);  // never destroyed: thread-local lanes may outlive statics
+    return *r;
+}
+bool pin_registry_acquire(const void* ptr, size_t bytes) { return pin_registry().acquire(ptr, bytes); }
+void pin_registry_release(const void* ptr) { pin_registry().release(ptr); }
 
-static void pin_sync_all_devices() {
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    for (int d = 0; d < group_size(); ++d) {
-        if (d && group_phys(d) == group_phys(d - 1)) continue;
-        (void)hipSetDevice(group_phys(d));
-        (void)hipDeviceSynchronize();
-    }
-    if (cur >= 0) (void)hipSetDevice(cur);
-}
-bool pin_registry_acquire(const void* ptr, size_t bytes) {
-    if (!ptr || !bytes) return false;
-    const uint8_t* lo = (const uint8_t*)ptr;
-    const uint8_t* hi = lo + bytes;
-    const std::thread::id me = std::this_thread::get_id();
-    constexpr long PIN_WAIT_MS = 2000;
-    long waited_ms = 0;
-    std::unique_lock<std::mutex> lk(g_pin_mu);
-    for (;;) {
-        // the registered intervals that touch [lo, hi)
-        std::vector<std::map<const uint8_t*, PinEntry>::iterator> hit;
-        auto it = g_pins.upper_bound(lo);
-        if (it != g_pins.begin()) --it;
-        for (; it != g_pins.end() && it->first < hi; ++it)
-            if (it->first + it->second.bytes > lo) hit.push_back(it);
-        if (hit.empty()) {
-            if (hipHostRegister(const_cast<void*>(ptr), bytes, hipHostRegisterPortable) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;  // exotic memory: the copies block the caller instead
-            }
-            PinEntry e{bytes, {}};
-            e.holders[me] = 1;
-            g_pins[lo] = e;
-            return true;
-        }
-        if (hit.size() == 1 && hit[0]->first <= lo && hit[0]->first + hit[0]->second.bytes >= hi) {
-            ++hit[0]->second.holders[me];
-            return true;
-        }
-        bool others = false;
-        for (auto& h : hit)
-            for (const auto& who : h->second.holders)
-                if (who.first != me && who.second) others = true;
-        if (others) {
-            // Never wait unboundedly: two threads that each hold a range and ask for one overlapping the other's, or a
-            // worker that waits here while its dispatcher holds the fan-out lock another holder is queued for, would wait for ever.  After
-            // PIN_WAIT_MS in all the request goes on WITHOUT a registration of its own - the caller's copies then take the runtime's
-            // pageable path (they block the calling thread), as they do when a registration fails.
-            if (waited_ms >= PIN_WAIT_MS) return false;
-            const auto t0 = std::chrono::steady_clock::now();
-            (void)g_pin_cv.wait_for(lk, std::chrono::milliseconds(PIN_WAIT_MS - waited_ms));  // a release wakes us; then look again
-            waited_ms += (long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() + 1;
-            continue;
-        }
-        // every interval in the way is held by this thread alone: replace them by their union with the request
-        const uint8_t* ulo = lo;
-        const uint8_t* uhi = hi;
-        unsigned mine = 1;
-        for (auto& h : hit) {
-            if (h->first < ulo) ulo = h->first;
-            if (h->first + h->second.bytes > uhi) uhi = h->first + h->second.bytes;
-            mine += h->second.refs();
-        }
-        lk.unlock();
-        pin_sync_all_devices();  // this thread's copies over the old intervals are complete
-        lk.lock();
-        // nobody else can have taken a hold meanwhile without waiting for us?  They can (a request INSIDE one of our intervals):
-        // look again in that case
-        bool changed = false;
-        for (auto& h : hit)
-            for (const auto& who : h->second.holders)
-                if (who.first != me && who.second) changed = true;
-        if (changed) continue;
-        for (auto& h : hit) {
-            (void)hipHostUnregister(const_cast<uint8_t*>(h->first));
-            g_pins.erase(h);
-        }
-        if (hipHostRegister(const_cast<uint8_t*>(ulo), (size_t)(uhi - ulo), hipHostRegisterPortable) != hipSuccess) {
-            (void)hipGetLastError();
-            // nothing of the union is registered now: this thread's earlier holds are gone with it (its copies become blocking
-            // ones, which is correct), and releases of them find no interval and do nothing
-            g_pin_cv.notify_all();
-            return false;
-        }
-        PinEntry e{(size_t)(uhi - ulo), {}};
-        e.holders[me] = mine;
-        g_pins[ulo] = e;
-        return true;
-    }
-}
-// ptr: any address a successful acquire was made with (it lies inside exactly one interval)
-void pin_registry_release(const void* ptr) {
-    const uint8_t* p = (const uint8_t*)ptr;
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    auto it = g_pins.upper_bound(p);
-    if (it == g_pins.begin()) return;
-    --it;
-    if (p >= it->first + it->second.bytes) return;
-    auto h = it->second.holders.find(std::this_thread::get_id());
-    if (h == it->second.holders.end()) return;  // not ours: a hold is released by the thread that took it (HostPin lives in one call object)
-    if (h->second && --h->second == 0) it->second.holders.erase(h);
-    if (it->second.refs() == 0) {
-        (void)hipHostUnregister(const_cast<uint8_t*>(it->first));
-        g_pins.erase(it);
-    }
-    g_pin_cv.notify_all();
-}
+static std::atomic<unsigned long long> g_lane_copies[LANE_ROUTES];
+void lane_count(int route) { g_lane_copies[route].fetch_add(1, std::memory_order_relaxed); }
 
 static int or_invalid_id(int rc) { return rc == PLK_NO_MATCH ? PLK_ERR_INVALID_ARG : rc; }
 int field_limbs(int field) {
@@ -428,6 +329,19 @@ void plk_shutdown(void) {
     (void)ntt_clear_cache_impl();
     scratch_clear();
     group_shutdown();
+}
+
+// Not part of the ABI (include/plonky_hip.h does not declare it): the suite reads which route the host-pointer plumbing took.
+// out[0 .. PIN_BRANCHES): calls per branch of the caller-buffer registry (pin_registry.h: PinBranch), then its waits and rechecks,
+// then the copies per LaneRoute (host_lane.h).  Returns the number of values there are; writes at most n of them.
+int plk_internal_host_stats(unsigned long long* out, unsigned n) {
+    const PinStats ps = pin_registry().stats();
+    std::vector<unsigned long long> v(ps.branch, ps.branch + PIN_BRANCHES);
+    v.push_back(ps.waits);
+    v.push_back(ps.rechecks);
+    for (int r = 0; r < LANE_ROUTES; ++r) v.push_back(g_lane_copies[r].load(std::memory_order_relaxed));
+    for (unsigned i = 0; out && i < n && i < v.size(); ++i) out[i] = v[i];
+    return (int)v.size();
 }
 
 const char* plk_last_error(void) { return last_error_ref().c_str(); }
@@ -513,9 +427,9 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
         for (unsigned b = 0; b < batch; ++b) {
             hipStream_t st = b % 3 == 0 ? l->stream : l->aux[b % 3 - 1];
             uint8_t* d = (uint8_t*)buf + b * bytes;
-            if (hipMemcpyAsync(d, in[b], bytes, hipMemcpyHostToDevice, st) != hipSuccess) return set_error(PLK_ERR_HIP, "upload of transform %u failed", b);
+            PLK_TRY(lane_h2d(*l, d, in[b], bytes, st));
             PLK_TRY(ntt_dev_impl(field, log_n, inverse, 1, d, d, st));
-            if (hipMemcpyAsync(out[b], d, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return set_error(PLK_ERR_HIP, "download of transform %u failed", b);
+            PLK_TRY(lane_d2h(*l, c.outs, out[b], d, bytes, st));
         }
     } else {
         while (l->ev_ready.size() < 2 * (size_t)batch) {
@@ -526,13 +440,13 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
         hipStream_t up = l->aux[0], down = l->aux[1];
         for (unsigned b = 0; b < batch; ++b) {
             uint8_t* d = (uint8_t*)buf + b * bytes;
-            if (hipMemcpyAsync(d, in[b], bytes, hipMemcpyHostToDevice, up) != hipSuccess) return set_error(PLK_ERR_HIP, "upload of transform %u failed", b);
+            PLK_TRY(lane_h2d(*l, d, in[b], bytes, up));  // >= 1 MiB: direct, or in chunks where the runtime rejects that (host_lane.h)
             PLK_HIP_TRY(hipEventRecord(l->ev_ready[2 * b], up));
             PLK_HIP_TRY(hipStreamWaitEvent(l->stream, l->ev_ready[2 * b], 0));
             PLK_TRY(ntt_dev_impl(field, log_n, inverse, 1, d, d, l->stream));
             PLK_HIP_TRY(hipEventRecord(l->ev_ready[2 * b + 1], l->stream));
             PLK_HIP_TRY(hipStreamWaitEvent(down, l->ev_ready[2 * b + 1], 0));
-            if (hipMemcpyAsync(out[b], d, bytes, hipMemcpyDeviceToHost, down) != hipSuccess) return set_error(PLK_ERR_HIP, "download of transform %u failed", b);
+            PLK_TRY(lane_d2h(*l, c.outs, out[b], d, bytes, down));
         }
     }
     PLK_TRY(lane_join(*l));  // before the registrations and the device buffer go
@@ -1298,9 +1212,8 @@ int plk_msm_execute_batch(plk_msm_ctx* ctx, unsigned batch, const uint64_t* cons
             l->ev_ready.push_back(e);
         }
         for (unsigned b = 0; b < batch; ++b) {
-            if (hipMemcpyAsync((uint8_t*)ds + b * sb, scalars[b], sb, hipMemcpyHostToDevice, l->aux[0]) != hipSuccess ||
-                hipEventRecord(l->ev_ready[b], l->aux[0]) != hipSuccess)
-                return set_error(PLK_ERR_HIP, "upload of scalar vector %u failed", b);
+            PLK_TRY(lane_h2d(*l, (uint8_t*)ds + b * sb, scalars[b], sb, l->aux[0]));
+            if (hipEventRecord(l->ev_ready[b], l->aux[0]) != hipSuccess) return set_error(PLK_ERR_HIP, "upload of scalar vector %u failed", b);
         }
         PLK_TRY(msm_execute_dev_impl(ctx, batch, ds, n_scalars, dxy, dz, l->stream, l->ev_ready.data()));
     }

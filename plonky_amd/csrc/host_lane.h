@@ -23,7 +23,12 @@ namespace plk {
 
 constexpr size_t PIN_CAP = (size_t)4 << 20;        // the staging buffer serves pieces up to this size
 constexpr size_t DIRECT_MIN = (size_t)64 << 10;    // larger pieces are copied straight from / to the caller's memory
+constexpr size_t BOUNCE_BYTES = (size_t)256 << 10;  // chunk of a copy the runtime would not take straight from / to the caller's memory
 constexpr int LANE_AUX = 2;
+
+// the route a copy from / to the caller's memory took, counted process-wide (capi.hip; read by the tests through plk_internal_host_stats)
+enum LaneRoute : int { LANE_STAGED = 0, LANE_DIRECT, LANE_BOUNCED, LANE_ROUTES };
+void lane_count(int route);
 
 struct HostLane {
     hipStream_t stream = nullptr;
@@ -33,6 +38,7 @@ struct HostLane {
     int device = -1;                                  // physical device the streams belong to
     uint8_t* pin = nullptr;
     size_t pin_bytes = 0, pin_used = 0;
+    uint8_t* bounce = nullptr;                        // BOUNCE_BYTES of pinned memory, allocated by the first rejected direct copy
     void drop_streams() {
         for (hipEvent_t e : ev_ready) (void)hipEventDestroy(e);
         ev_ready.clear();
@@ -49,6 +55,7 @@ struct HostLane {
     }
     ~HostLane() {
         if (pin) (void)hipHostFree(pin);
+        if (bounce) (void)hipHostFree(bounce);
         drop_streams();
     }
 };
@@ -85,7 +92,7 @@ inline int lane_join(HostLane& l) {
 // same time (the Rayon-style callers the lanes are built for) share ONE registration, released by whoever finishes last.  A request
 // that extends or partly overlaps a registered interval never leaves a half-registered range: it waits for other threads' holds to
 // end, or - the calling thread's own holds - re-registers the union after synchronising the devices.  Registration can still fail
-// (exotic memory): the copies then block the calling thread - same result.  Registered as portable: every device of the group may
+// (exotic memory, or memory the caller has registered itself): the copies then go unregistered - same result, see lane_h2d.  Registered as portable: every device of the group may
 // copy from it.  A hold is released by the thread that took it, with the address it was taken with.
 bool pin_registry_acquire(const void* ptr, size_t bytes);  // true: registered (by this call or an earlier one), must be released
 void pin_registry_release(const void* ptr);
@@ -128,6 +135,41 @@ inline uint8_t* lane_stage(HostLane& l, size_t bytes) {
     l.pin_used = need;
     return p;
 }
+// A direct copy the runtime rejects.  HIP resolves a host pointer to the registered object it starts in, and refuses a copy that runs
+// past that object's end: a caller buffer that starts inside memory the CALLER registered (hipHostRegister of its own, on a range
+// that does not cover the buffer), or inside another thread's registration this thread gave up waiting for (pin_registry.h).  Seen
+// on the MI355X with plk_ntt, which registers nothing itself; where the entry point registers the buffer (the batched calls) the
+// runtime accepted the overlapping registration and the direct copy with it.  Of the two ways out - blocking
+// copies of pieces cut at the foreign registration's end, or chunks through pinned memory of the lane's own - the SECOND is taken: it
+// needs no knowledge of where the foreign registration ends, and is the same for every reason of the rejection.  The chunks go
+// through a bounce buffer of their own (the staging buffer may be full of pieces still in flight), one at a time, the stream
+// synchronised after each: slow, blocking, and exact.  Both directions.
+inline int lane_bounce(HostLane& l) {
+    if (!l.bounce) PLK_HIP_TRY(hipHostMalloc((void**)&l.bounce, BOUNCE_BYTES, hipHostMallocPortable));
+    return PLK_OK;
+}
+inline int lane_h2d_bounced(HostLane& l, void* d, const void* h, size_t bytes, hipStream_t st) {
+    PLK_TRY(lane_bounce(l));
+    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
+        const size_t n = bytes - off < BOUNCE_BYTES ? bytes - off : BOUNCE_BYTES;
+        memcpy(l.bounce, (const uint8_t*)h + off, n);
+        PLK_HIP_TRY(hipMemcpyAsync((uint8_t*)d + off, l.bounce, n, hipMemcpyHostToDevice, st));
+        PLK_HIP_TRY(hipStreamSynchronize(st));
+    }
+    lane_count(LANE_BOUNCED);
+    return PLK_OK;
+}
+inline int lane_d2h_bounced(HostLane& l, void* h, const void* d, size_t bytes, hipStream_t st) {
+    PLK_TRY(lane_bounce(l));
+    for (size_t off = 0; off < bytes; off += BOUNCE_BYTES) {
+        const size_t n = bytes - off < BOUNCE_BYTES ? bytes - off : BOUNCE_BYTES;
+        PLK_HIP_TRY(hipMemcpyAsync(l.bounce, (const uint8_t*)d + off, n, hipMemcpyDeviceToHost, st));
+        PLK_HIP_TRY(hipStreamSynchronize(st));  // everything enqueued on st before this copy has run: the data is final
+        memcpy((uint8_t*)h + off, l.bounce, n);
+    }
+    lane_count(LANE_BOUNCED);
+    return PLK_OK;
+}
 inline int lane_h2d(HostLane& l, void* d, const void* h, size_t bytes, hipStream_t st = nullptr) {
     if (!bytes) return PLK_OK;
     if (!st) st = l.stream;
@@ -135,8 +177,13 @@ inline int lane_h2d(HostLane& l, void* d, const void* h, size_t bytes, hipStream
     if (stg) {
         memcpy(stg, h, bytes);
         PLK_HIP_TRY(hipMemcpyAsync(d, stg, bytes, hipMemcpyHostToDevice, st));
+        lane_count(LANE_STAGED);
+    } else if (const hipError_t e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st)) {  // pageable or registered: the pinned rate either way
+        (void)hipGetLastError();
+        set_error(PLK_OK, "direct upload of %zu bytes rejected (%s): copied in chunks", bytes, hipGetErrorString(e));  // a note, not a failure
+        return lane_h2d_bounced(l, d, h, bytes, st);
     } else {
-        PLK_HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));  // pageable or registered: the pinned rate either way
+        lane_count(LANE_DIRECT);
     }
     return PLK_OK;
 }
@@ -153,8 +200,13 @@ inline int lane_d2h(HostLane& l, std::vector<LaneOut>& outs, void* h, const void
     if (stg) {
         PLK_HIP_TRY(hipMemcpyAsync(stg, d, bytes, hipMemcpyDeviceToHost, st));
         outs.push_back({stg, h, bytes});
+        lane_count(LANE_STAGED);
+    } else if (const hipError_t e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st)) {
+        (void)hipGetLastError();
+        set_error(PLK_OK, "direct download of %zu bytes rejected (%s): copied in chunks", bytes, hipGetErrorString(e));
+        return lane_d2h_bounced(l, h, d, bytes, st);  // see lane_h2d_bounced
     } else {
-        PLK_HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st));
+        lane_count(LANE_DIRECT);
     }
     return PLK_OK;
 }
