@@ -64,7 +64,6 @@ int msm_set_profiling_impl(plk_msm_ctx* ctx, int enable);
 int msm_get_timings_impl(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
 int ntt_set_profiling_impl(int enable);
 int ntt_get_timings_impl(double* sum_ms, unsigned* launches);
-int poly_clear_cache_impl();
 int poly_divide_by_z_h_dev_impl(int field, const void* d_coeffs, size_t len, size_t n, void* d_out, size_t out_cap, size_t* out_len,
                                 hipStream_t stream);
 int poly_mul_dev_impl(int field, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t out_cap, size_t* out_len,
@@ -324,9 +323,7 @@ int plk_multi_plan(unsigned world, unsigned batch, size_t n, unsigned device, un
 }
 
 void plk_shutdown(void) {
-    (void)plonk_clear_cache_impl();
-    (void)poly_clear_cache_impl();
-    (void)ntt_clear_cache_impl();
+    table_caches_clear();
     scratch_clear();
     group_shutdown();
 }
@@ -363,11 +360,9 @@ int plk_curve_scalar_field(int curve) { return curve_scalar_field(curve); }
 int plk_ntt_precompute(int field, unsigned log_n) { PLK_API; return ntt_precompute_impl(field, log_n); }
 int plk_ntt_clear_cache(void) {
     PLK_API;
-    (void)plonk_clear_cache_impl();
-    (void)poly_clear_cache_impl();
-    const int rc = ntt_clear_cache_impl();
+    table_caches_clear();
     scratch_clear();  // "memory pressure": the idle scratch buffers go as well
-    return rc;
+    return PLK_OK;
 }
 
 int plk_ntt_precompute_table_dev(int field, unsigned log_n, void* d_out, void* stream) {

@@ -12,6 +12,7 @@
 
 #include "../../include/plonky_hip.h"
 #include "dispatch.cuh"
+#include "table_cache.h"
 
 namespace plk {
 
@@ -88,9 +89,22 @@ int run_on_devices(int count, const std::function<int(int)>& fn);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// RAII device buffer for the host-pointer entry points
+// RAII device buffer: the host-pointer entry points' copies and every buffer of a cached table struct (table_cache.h).  Movable, not
+// copyable: a copy would free the buffer twice.
 struct DevBuf {
     void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            if (p) (void)hipFree(p);
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
@@ -154,7 +168,6 @@ struct NttHooks {
 
 // ---- entry points implemented in ntt.hip / msm.hip / fieldops.hip, wrapped by capi.hip ----
 int ntt_precompute_impl(int field, unsigned log_n);
-int ntt_clear_cache_impl();
 int ntt_dev_impl(int field, unsigned log_n, int inverse, unsigned batch, const void* d_in, void* d_out, hipStream_t stream);
 int ntt_dev_hooked_impl(int field, unsigned log_n, int inverse, unsigned batch, const void* d_in, void* d_out, const NttHooks& hooks,
                         hipStream_t stream);
@@ -164,8 +177,6 @@ int ntt_dev_hooked_impl(int field, unsigned log_n, int inverse, unsigned batch, 
 // been synchronised or the hold is released after them (a concurrent plk_ntt_clear_cache frees the table otherwise)
 int ntt_plan_pow_table(int field, unsigned log_n, const void** pw, int* log_t, std::shared_ptr<const void>* hold = nullptr);
 int ntt_reference_table_dev_impl(int field, unsigned log_n, void* d_out, hipStream_t stream);
-int plonk_clear_cache_impl();
-void plookup_clear_cache();  // the Plookup tables (plookup.hip); plonk_clear_cache_impl drops them with its own
 int field_inner_product_dev_impl(int field, const void* d_a, const void* d_b, size_t count, void* d_out, hipStream_t stream);
 int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, const uint64_t* s_lo, const uint64_t* s_hi, size_t count, void* d_out,
                                hipStream_t stream);

@@ -215,6 +215,36 @@ template <class P> __global__ void k_plonk_xs(const uint4* __restrict__ pw, int 
         for (int i = 0; i < LZ_TOP_STRIDE; ++i) top[tt * LZ_TOP_STRIDE + i] = i < FzCfg<P>::NZ ? z.l[i] : 0u;
     }
 }
+// what k_plonk_xs fills for a domain of 2^log_domain points (g its primitive root): the start of the Plonk tables (8n points) and
+// of the Plookup ones (4N points)
+struct DomainTables {
+    DevBuf xs_lo;    // g^j, j < 1024, R-form: feeds the Lagrange table of the family
+    DevBuf xs_hi;    // g^(1024 j)
+    DevBuf xs_lo_z;  // the same two tables in R'-form: the point x of a lane is one product of them
+    DevBuf xs_hi_z;
+    DevBuf small;    // [0..7]: 1/1 .. 1/7 then unused, R'-form; MDS entry (r, c) = 1 / (4 + r - c)  (mds.rs:63-77)
+    DevBuf top;      // (t 2^(S + 5)) mod p, t < LZ_TOP_ROWS, plain integers in 29-bit limbs (lz_from_rform)
+};
+// Allocates and fills them on `stream`, asynchronously.  The power table of the NTT plan is only borrowed for the launch: the caller
+// keeps plan_hold until it has synchronised the stream.
+template <class P> int build_domain_tables(int log_domain, hipStream_t stream, DomainTables& t, std::shared_ptr<const void>& plan_hold) {
+    const void* pw = nullptr;
+    int log_t = 0;
+    PLK_TRY(ntt_plan_pow_table(P::FIELD_ID, (unsigned)log_domain, &pw, &log_t, &plan_hold));
+    const size_t n_lo = (size_t)1 << XS_LO_LOG, n_hi = log_domain > XS_LO_LOG ? (size_t)1 << (log_domain - XS_LO_LOG) : 1;
+    PLK_TRY(t.xs_lo.alloc(n_lo * 32));
+    PLK_TRY(t.xs_hi.alloc(n_hi * 32));
+    PLK_TRY(t.xs_lo_z.alloc(n_lo * 32));
+    PLK_TRY(t.xs_hi_z.alloc(n_hi * 32));
+    PLK_TRY(t.small.alloc(8 * 32));
+    PLK_TRY(t.top.alloc((size_t)LZ_TOP_ROWS * LZ_TOP_STRIDE * 4));
+    const size_t cnt = n_lo + n_hi + 7 + LZ_TOP_ROWS;
+    k_plonk_xs<P><<<(unsigned)((cnt + 127) / 128), 128, 0, stream>>>((const uint4*)pw, log_t, log_domain, (uint4*)t.xs_lo.p, (uint4*)t.xs_hi.p, (uint4*)t.xs_lo_z.p,
+                                                                     (uint4*)t.xs_hi_z.p, (uint4*)t.small.p, (uint32_t*)t.top.p);
+    PLK_HIP_TRY(hipGetLastError());
+    return PLK_OK;
+}
+
 template <class P> PLK_DI Fe<P> plonk_x(const uint4* lo, const uint4* hi, size_t i) {
     const Fe<P> a = fe_load<P>(lo + (i & (((size_t)1 << XS_LO_LOG) - 1)) * 2);
     if ((i >> XS_LO_LOG) == 0) return a;

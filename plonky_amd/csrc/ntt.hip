@@ -21,7 +21,6 @@
 // limbs are bit-identical.  iNTT = the same passes with w^-1 tables and n^-1 folded into the
 // first inter-pass twiddle table (instead of the index-reversal trick of fft.rs:90-99).
 #include <cstdlib>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <tuple>
@@ -588,17 +587,9 @@ __global__ void PLK_NTT_BOUNDS k_ntt_pass(const void* in, void* out, const uint4
 struct NttPlan {
     int field = 0, log_n = 0, device = 0;
     std::vector<int> pass_log;            // a_1 .. a_m
-    void* pw = nullptr;                   // 65 elements (see k_ntt_pow2)
-    void* inner[2] = {nullptr, nullptr};  // forward / inverse stage twiddles
-    std::vector<void*> outer[2];          // per non-last pass
-    ~NttPlan() {
-        if (pw) (void)hipFree(pw);
-        for (int d = 0; d < 2; ++d) {
-            if (inner[d]) (void)hipFree(inner[d]);
-            for (void* p : outer[d])
-                if (p) (void)hipFree(p);
-        }
-    }
+    DevBuf pw;                            // 65 elements (see k_ntt_pow2)
+    DevBuf inner[2];                      // forward / inverse stage twiddles
+    std::vector<DevBuf> outer[2];         // per non-last pass
 };
 
 static std::vector<int> plan_passes(int log_n) {
@@ -675,29 +666,28 @@ int ntt_get_timings_impl(double* sum_ms, unsigned* launches) {
     return PLK_OK;
 }
 
-static std::mutex g_plan_mu;
-static std::map<std::tuple<int, int, int>, std::shared_ptr<NttPlan>> g_plans;
+static TableCache<std::tuple<int, int, int>, NttPlan> g_plans;  // (device, field, log_n)
 
 template <class P> static int build_plan_t(NttPlan& pl) {
     const int log_n = pl.log_n;
     const int log_t = log_n > INNER_LOG ? log_n : INNER_LOG;
     if (log_t > P::TWO_ADICITY) return set_error(PLK_ERR_TWO_ADICITY, "log_n %d exceeds the field's 2-adicity %d", log_n, P::TWO_ADICITY);
-    PLK_HIP_TRY(hipMalloc(&pl.pw, 67 * (size_t)P::NL * 4));
-    k_ntt_pow2<P><<<1, 64>>>((uint4*)pl.pw, log_t, log_n);
+    PLK_TRY(pl.pw.alloc(67 * (size_t)P::NL * 4));
+    k_ntt_pow2<P><<<1, 64>>>((uint4*)pl.pw.p, log_t, log_n);
     PLK_HIP_TRY(hipGetLastError());
     const int m = (int)pl.pass_log.size();
     for (int dir = 0; dir < 2; ++dir) {
-        PLK_HIP_TRY(hipMalloc(&pl.inner[dir], (size_t)(1 << (INNER_LOG - 1)) * P::NL * 4));
-        k_ntt_fill_inner<P><<<((1 << (INNER_LOG - 1)) + 255) / 256, 256>>>((uint4*)pl.inner[dir], (const uint4*)pl.pw, log_t, dir);
+        PLK_TRY(pl.inner[dir].alloc((size_t)(1 << (INNER_LOG - 1)) * P::NL * 4));
+        k_ntt_fill_inner<P><<<((1 << (INNER_LOG - 1)) + 255) / 256, 256>>>((uint4*)pl.inner[dir].p, (const uint4*)pl.pw.p, log_t, dir);
         PLK_HIP_TRY(hipGetLastError());
         int log_nt = log_n;
         for (int t = 0; t + 1 < m; ++t) {
             const int log_s = log_nt - pl.pass_log[t];
-            void* tab = nullptr;
-            PLK_HIP_TRY(hipMalloc(&tab, limb_bytes((size_t)1 << log_nt, FzCfg<P>::NZ)));
-            pl.outer[dir].push_back(tab);
+            pl.outer[dir].emplace_back();
+            DevBuf& tab = pl.outer[dir].back();
+            PLK_TRY(tab.alloc(limb_bytes((size_t)1 << log_nt, FzCfg<P>::NZ)));
             const size_t cnt = (size_t)1 << log_nt;
-            k_ntt_fill_outer<P><<<(unsigned)((cnt + 255) / 256), 256>>>((uint32_t*)tab, (const uint4*)pl.pw, log_t, log_nt, log_s, dir,
+            k_ntt_fill_outer<P><<<(unsigned)((cnt + 255) / 256), 256>>>((uint32_t*)tab.p, (const uint4*)pl.pw.p, log_t, log_nt, log_s, dir,
                                                                         (dir == 1 && t == 0) ? 1 : 0);
             PLK_HIP_TRY(hipGetLastError());
             log_nt = log_s;
@@ -711,34 +701,19 @@ static int get_plan(int field, unsigned log_n, std::shared_ptr<NttPlan>& out) {
     PLK_TRY(ensure_device());
     int dev = 0;
     PLK_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto key = std::make_tuple(dev, field, (int)log_n);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) {
-        out = it->second;
-        return PLK_OK;
-    }
-    auto pl = std::make_shared<NttPlan>();
-    pl->field = field;
-    pl->log_n = (int)log_n;
-    pl->device = dev;
-    pl->pass_log = plan_passes((int)log_n);
-    PLK_TRY(or_invalid(with_field(field, [&](auto t) { return build_plan_t<tag_t<decltype(t)>>(*pl); }), "field %d has no NTT entry point", field));
-    g_plans[key] = pl;
-    out = pl;
-    return PLK_OK;
+    return g_plans.get(std::make_tuple(dev, field, (int)log_n), out, [&](NttPlan& pl) {
+        pl.field = field;
+        pl.log_n = (int)log_n;
+        pl.device = dev;
+        pl.pass_log = plan_passes((int)log_n);
+        return or_invalid(with_field(field, [&](auto t) { return build_plan_t<tag_t<decltype(t)>>(pl); }), "field %d has no NTT entry point", field);
+    });
 }
 
 int ntt_precompute_impl(int field, unsigned log_n) {
     if (log_n > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_n %u too large (max 30)", log_n);
     std::shared_ptr<NttPlan> pl;
     return get_plan(field, log_n, pl);
-}
-
-int ntt_clear_cache_impl() {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    g_plans.clear();
-    return PLK_OK;
 }
 
 template <class P>
@@ -787,7 +762,7 @@ static int run_plan_t(const NttPlan& pl, int inverse, unsigned batch, const void
             a.skip = k;
         }
         const size_t tiles = (((size_t)1 << log_n) >> (a.log_a + a.log_q)) * batch;
-        const void* outer = a.last ? nullptr : pl.outer[dir][t];
+        const void* outer = a.last ? nullptr : pl.outer[dir][t].p;
         void* dst = a.last ? d_out : scratch;
         std::pair<hipEvent_t, hipEvent_t> pev;
         const bool prof = prof_begin(stream, pev);
@@ -812,7 +787,7 @@ static int run_plan_t(const NttPlan& pl, int inverse, unsigned batch, const void
             a.stagger = (quanta > 0 && tiles > (size_t)cus && tiles <= (size_t)4 * cus) ? quanta : 0;
             a.stagger_div = cus;
         }
-        const uint4* scale = (const uint4*)pl.pw + (a.scale ? 66 : 65) * EU<P>();
+        const uint4* scale = (const uint4*)pl.pw.p + (a.scale ? 66 : 65) * EU<P>();
         const bool use_hooks = hooks && (a.first || a.last);
         const NttHooks hk = use_hooks ? *hooks : NttHooks{};
         const unsigned tl = (unsigned)tiles;
@@ -824,7 +799,7 @@ static int run_plan_t(const NttPlan& pl, int inverse, unsigned batch, const void
     do {                                                                                                                                      \
         if (lds_bytes > 64 * 1024)                                                                                                            \
             (void)hipFuncSetAttribute((const void*)k_ntt_pass<P, H, IL, OL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);     \
-        k_ntt_pass<P, H, IL, OL><<<tl, NTT_THREADS, lds_bytes, stream>>>(src, dst, (const uint4*)pl.inner[dir], otw, scale, a, hk);           \
+        k_ntt_pass<P, H, IL, OL><<<tl, NTT_THREADS, lds_bytes, stream>>>(src, dst, (const uint4*)pl.inner[dir].p, otw, scale, a, hk);         \
     } while (0)
         if (a.first && a.last) {
             if (use_hooks) PLK_NTT_LAUNCH(true, false, false); else PLK_NTT_LAUNCH(false, false, false);
@@ -885,7 +860,7 @@ int ntt_reference_table_dev_impl(int field, unsigned log_n, void* d_out, hipStre
     const size_t total = ((size_t)2 << log_n) - 1;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     PLK_TRY(or_bad_field(with_field(field, [&](auto t) {
-        k_ntt_reference_table<tag_t<decltype(t)>><<<blocks, 256, 0, stream>>>((uint4*)d_out, (const uint4*)pl->pw, log_t, (int)log_n);
+        k_ntt_reference_table<tag_t<decltype(t)>><<<blocks, 256, 0, stream>>>((uint4*)d_out, (const uint4*)pl->pw.p, log_t, (int)log_n);
         return PLK_OK;
     }), field));
     PLK_HIP_TRY(hipGetLastError());
@@ -897,7 +872,7 @@ int ntt_reference_table_dev_impl(int field, unsigned log_n, void* d_out, hipStre
 int ntt_plan_pow_table(int field, unsigned log_n, const void** pw, int* log_t, std::shared_ptr<const void>* hold) {
     std::shared_ptr<NttPlan> pl;
     PLK_TRY(get_plan(field, log_n, pl));
-    *pw = pl->pw;  // owned by the plan: alive while the cache or *hold references it
+    *pw = pl->pw.p;  // owned by the plan: alive while the cache or *hold references it
     if (hold) *hold = pl;
     *log_t = (int)log_n > INNER_LOG ? (int)log_n : INNER_LOG;
     return PLK_OK;

@@ -17,9 +17,7 @@
 // bit-identical to the reference's (field arithmetic is exact and associative; only the grouping differs).
 // get_subgroup_shift (partition.rs:140-153) draws its k_i from ChaCha8: they are inputs here.
 #include <cstdlib>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <tuple>
 
 #include "common.h"
@@ -36,28 +34,10 @@ constexpr int GRID_WIDTH = 65;       // plonk.rs:25
 constexpr int NUM_TERMS = 8;         // the longest gate constraint list (base_4_sum: 1 + 7, rescue_a: 8)
 
 // circuit-size tables (device, field, log_degree): everything the loop needs that does not depend on the proof
-struct PlonkTables {
-    void* xs_lo = nullptr;    // g^j, j < 1024 (g = primitive 8n-th root, circuit_builder.rs:1122), R-form: feeds the L_1 table
-    void* xs_hi = nullptr;    // g^(1024 j)
-    void* xs_lo_z = nullptr;  // the same two tables in R'-form: the point x of a lane is one product of them
-    void* xs_hi_z = nullptr;
-    void* l1 = nullptr;       // L_1(g^i), i < 8n  (plonk_util.rs:14-24), R'-form
-    void* small = nullptr;    // [0..7]: 1/1 .. 1/7 then unused, R'-form; MDS entry (r, c) = 1 / (4 + r - c)  (mds.rs:63-77)
-    void* top = nullptr;      // (t 2^(S + 5)) mod p, t < LZ_TOP_ROWS, plain integers in 29-bit limbs (lz_from_rform)
-    ~PlonkTables() {
-        for (void* p : {xs_lo, xs_hi, xs_lo_z, xs_hi_z, l1, small, top})
-            if (p) (void)hipFree(p);
-    }
+struct PlonkTables : DomainTables {  // the domain of the primitive 8n-th root g (circuit_builder.rs:1122)
+    DevBuf l1;                       // L_1(g^i), i < 8n  (plonk_util.rs:14-24), R'-form
 };
-static std::mutex g_plonk_mu;
-static std::map<std::tuple<int, int, int>, std::shared_ptr<PlonkTables>> g_plonk;
-
-int plonk_clear_cache_impl() {
-    plookup_clear_cache();
-    std::lock_guard<std::mutex> lk(g_plonk_mu);
-    g_plonk.clear();
-    return PLK_OK;
-}
+static TableCache<std::tuple<int, int, int>, PlonkTables> g_plonk;
 
 // L_1(x) = (x^n - 1) / (n (x - 1)), L_1(1) = 1; eight points per lane share one inversion (Montgomery's trick)
 constexpr int L1_PER_LANE = 8;
@@ -96,38 +76,18 @@ template <class P> __global__ void __launch_bounds__(64) k_plonk_l1(const uint4*
 template <class P> static int get_plonk_tables(int log_degree, hipStream_t stream, std::shared_ptr<PlonkTables>& out) {
     int dev = 0;
     PLK_HIP_TRY(hipGetDevice(&dev));
-    const int log_n8 = log_degree + 3;
-    std::lock_guard<std::mutex> lk(g_plonk_mu);
-    const auto key = std::make_tuple(dev, (int)P::FIELD_ID, log_degree);
-    auto it = g_plonk.find(key);
-    if (it != g_plonk.end()) {
-        out = it->second;
+    return g_plonk.get(std::make_tuple(dev, (int)P::FIELD_ID, log_degree), out, [&](PlonkTables& t) {
+        const int log_n8 = log_degree + 3;
+        const size_t n8 = (size_t)1 << log_n8;
+        std::shared_ptr<const void> plan_hold;  // keeps the plan (and its power table) alive across the two launches
+        PLK_TRY(build_domain_tables<P>(log_n8, stream, t, plan_hold));
+        PLK_TRY(t.l1.alloc(n8 * 32));
+        const size_t lanes = (n8 + L1_PER_LANE - 1) / L1_PER_LANE;
+        k_plonk_l1<P><<<(unsigned)((lanes + 63) / 64), 64, 0, stream>>>((const uint4*)t.xs_lo.p, (const uint4*)t.xs_hi.p, log_degree, (uint4*)t.l1.p);
+        PLK_HIP_TRY(hipGetLastError());
+        PLK_HIP_TRY(hipStreamSynchronize(stream));  // the power table of the plan is only borrowed for these two launches
         return PLK_OK;
-    }
-    const void* pw = nullptr;
-    int log_t = 0;
-    std::shared_ptr<const void> plan_hold;  // keeps the plan (and its power table) alive across the two launches below
-    PLK_TRY(ntt_plan_pow_table(P::FIELD_ID, (unsigned)log_n8, &pw, &log_t, &plan_hold));
-    auto t = std::make_shared<PlonkTables>();
-    const size_t n8 = (size_t)1 << log_n8;
-    const size_t n_lo = (size_t)1 << XS_LO_LOG, n_hi = log_n8 > XS_LO_LOG ? (size_t)1 << (log_n8 - XS_LO_LOG) : 1;
-    PLK_HIP_TRY(hipMalloc(&t->xs_lo, n_lo * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_hi, n_hi * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_lo_z, n_lo * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_hi_z, n_hi * 32));
-    PLK_HIP_TRY(hipMalloc(&t->small, 8 * 32));
-    PLK_HIP_TRY(hipMalloc(&t->l1, n8 * 32));
-    PLK_HIP_TRY(hipMalloc(&t->top, (size_t)LZ_TOP_ROWS * LZ_TOP_STRIDE * 4));
-    const size_t cnt = n_lo + n_hi + 7 + LZ_TOP_ROWS;
-    k_plonk_xs<P><<<(unsigned)((cnt + 127) / 128), 128, 0, stream>>>((const uint4*)pw, log_t, log_n8, (uint4*)t->xs_lo, (uint4*)t->xs_hi, (uint4*)t->xs_lo_z,
-                                                                     (uint4*)t->xs_hi_z, (uint4*)t->small, (uint32_t*)t->top);
-    const size_t lanes = (n8 + L1_PER_LANE - 1) / L1_PER_LANE;
-    k_plonk_l1<P><<<(unsigned)((lanes + 63) / 64), 64, 0, stream>>>((const uint4*)t->xs_lo, (const uint4*)t->xs_hi, log_degree, (uint4*)t->l1);
-    PLK_HIP_TRY(hipGetLastError());
-    PLK_HIP_TRY(hipStreamSynchronize(stream));  // the power table of the plan is only borrowed for these two launches
-    g_plonk[key] = t;
-    out = t;
-    return PLK_OK;
+    });
 }
 
 // the R-form powers of the 8n-th root for sigma.hip: g_n^r = plonk_x(xs_lo, xs_hi, 8 r); *hold shares ownership of the tables
@@ -135,8 +95,8 @@ int plonk_domain_powers(int field, unsigned log_degree, hipStream_t stream, cons
     return with_field4(field, [&](auto tag) {
         std::shared_ptr<PlonkTables> t;
         PLK_TRY(get_plonk_tables<tag_t<decltype(tag)>>((int)log_degree, stream, t));
-        *xs_lo = t->xs_lo;
-        *xs_hi = t->xs_hi;
+        *xs_lo = t->xs_lo.p;
+        *xs_hi = t->xs_hi.p;
         *hold = t;
         return (int)PLK_OK;
     });
@@ -576,7 +536,7 @@ static int vanishing_points_t(unsigned log_degree, const void* d_constants, cons
         scratch_release(part, stream);
         return PLK_ERR_OOM;
     }
-    k_plonk_weights<P><<<1, 64, 0, stream>>>((const uint4*)t->small, sc, weights);
+    k_plonk_weights<P><<<1, 64, 0, stream>>>((const uint4*)t->small.p, sc, weights);
     // PLK_VANISH_SLAB_LOG=k: the launches walk the domain in slabs of 2^k points, so that the rows a slab reads (29 x 32 B per
     // point) are still in the 256 MiB Infinity Cache when the next launch of the slab re-reads them (round-3 review item 5;
     // measured in DESIGN.md section 4c).  Default: the whole domain per launch.
@@ -588,8 +548,8 @@ static int vanishing_points_t(unsigned log_degree, const void* d_constants, cons
     const size_t slab = slab_log ? ((size_t)1 << slab_log) : n8;
 #define PLK_VANISH(PASS)                                                                                                                                  \
     k_vanishing_points<P, PASS><<<blocks, 128, 0, stream>>>((const uint4*)d_constants, (const uint4*)d_wires, (const uint4*)d_s_sigma, (const uint4*)d_z, \
-                                                            (const uint4*)t->xs_lo_z, (const uint4*)t->xs_hi_z, (const uint4*)t->l1, (const uint4*)t->small, sc, \
-                                                            (int)log_degree, (uint32_t*)part, (uint4*)d_out, first, cnt, weights, (const uint32_t*)t->top)
+                                                            (const uint4*)t->xs_lo_z.p, (const uint4*)t->xs_hi_z.p, (const uint4*)t->l1.p, (const uint4*)t->small.p, sc, \
+                                                            (int)log_degree, (uint32_t*)part, (uint4*)d_out, first, cnt, weights, (const uint32_t*)t->top.p)
     for (size_t first = 0; first < n8; first += slab) {
         const size_t cnt = n8 - first < slab ? n8 - first : slab;
         const unsigned blocks = (unsigned)((cnt + 127) / 128);
@@ -640,7 +600,7 @@ static int all_constraints_t(size_t count, const void* d_constants, const void* 
     std::shared_ptr<PlonkTables> t;
     PLK_TRY(get_plonk_tables<P>(7, stream, t));  // only the small inverses are used: any circuit size serves
     k_all_constraints<P><<<(unsigned)((count + 127) / 128), 128, 0, stream>>>((const uint4*)d_constants, (const uint4*)d_local, (const uint4*)d_right,
-                                                                             (const uint4*)d_below, (const uint4*)t->small, sc, count, (uint4*)d_out);
+                                                                             (const uint4*)d_below, (const uint4*)t->small.p, sc, count, (uint4*)d_out);
     PLK_HIP_TRY(hipGetLastError());
     return PLK_OK;
 }
@@ -775,9 +735,9 @@ static int permutation_z_t(unsigned log_degree, const void* d_wires, const void*
     }
     hipError_t e = hipMemsetAsync(zeros, 0, 2 * sizeof(unsigned), stream);
     if (e == hipSuccess) {
-        k_perm_rows<P><<<(unsigned)tiles, PERM_LANES, 0, stream>>>((const uint4*)d_wires, (const uint4*)d_s_sigma, sigma_stride, (const uint4*)t->xs_lo_z,
-                                                                   (const uint4*)t->xs_hi_z, sc, (int)log_degree, (uint4*)d_out, tile_tot, zeros,
-                                                                   (const uint32_t*)t->top);
+        k_perm_rows<P><<<(unsigned)tiles, PERM_LANES, 0, stream>>>((const uint4*)d_wires, (const uint4*)d_s_sigma, sigma_stride, (const uint4*)t->xs_lo_z.p,
+                                                                   (const uint4*)t->xs_hi_z.p, sc, (int)log_degree, (uint4*)d_out, tile_tot, zeros,
+                                                                   (const uint32_t*)t->top.p);
         k_perm_tiles<P><<<1, PERM_SCAN_LANES, 0, stream>>>(tile_tot, tiles, zeros, (uint32_t*)d_status);
         k_perm_fix<P><<<(unsigned)((n + 255) / 256), 256, 0, stream>>>((uint4*)d_out, tile_tot, n);
         e = hipGetLastError();

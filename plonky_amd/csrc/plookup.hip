@@ -15,9 +15,7 @@
 //
 // The arithmetic is the Lz working form of lz.cuh: exact modulo p, reduced to the unique representative at the end, so the results
 // are bit-identical to the reference's whatever the grouping.
-#include <map>
 #include <memory>
-#include <mutex>
 #include <tuple>
 #include <utility>
 
@@ -35,26 +33,10 @@ template <int N, class F> PLK_DI void lkp_static_for(F&& f) { lkp_static_for_imp
 // ---------------------------------------------------------------------------------------------
 // tables (device, field, log of the domain): powers of g4 in both forms, L_0 over the domain, the table of lz_from_rform
 // ---------------------------------------------------------------------------------------------
-struct LookupTables {
-    void* xs_lo = nullptr;    // g4^j, j < 1024, R-form: feeds the L_0 table
-    void* xs_hi = nullptr;    // g4^(1024 j)
-    void* xs_lo_z = nullptr;  // the same in R'-form: the point x of a lane is one product of them
-    void* xs_hi_z = nullptr;
-    void* small = nullptr;    // written by k_plonk_xs, not read here
-    void* l0 = nullptr;       // eval_l_i(N, 0, w, g4^i), i < 4N, R'-form; 0 at every i = 0 (mod 4)
-    void* top = nullptr;      // (t 2^(S + 5)) mod p (lz_from_rform)
-    ~LookupTables() {
-        for (void* p : {xs_lo, xs_hi, xs_lo_z, xs_hi_z, small, l0, top})
-            if (p) (void)hipFree(p);
-    }
+struct LookupTables : DomainTables {  // the domain of g4; `small` is not read here
+    DevBuf l0;                        // eval_l_i(N, 0, w, g4^i), i < 4N, R'-form; 0 at every i = 0 (mod 4)
 };
-static std::mutex g_lookup_mu;
-static std::map<std::tuple<int, int, int>, std::shared_ptr<LookupTables>> g_lookup;
-
-void plookup_clear_cache() {
-    std::lock_guard<std::mutex> lk(g_lookup_mu);
-    g_lookup.clear();
-}
+static TableCache<std::tuple<int, int, int>, LookupTables> g_lookup;
 
 // N (x - 1) for the batch inversion, R-form; 1 where the table is 0 anyway (x = 1 has no inverse)
 template <class P> __global__ void __launch_bounds__(128) k_lookup_l0_den(const uint4* __restrict__ lo, const uint4* __restrict__ hi, int log_size,
@@ -82,48 +64,27 @@ template <class P> __global__ void __launch_bounds__(128) k_lookup_l0(const uint
 template <class P> static int get_lookup_tables(int log_size, hipStream_t stream, std::shared_ptr<LookupTables>& out) {
     int dev = 0;
     PLK_HIP_TRY(hipGetDevice(&dev));
-    const bool points = log_size > 0;
-    const int log_n4 = points ? log_size + 2 : XS_LO_LOG;
-    std::lock_guard<std::mutex> lk(g_lookup_mu);
-    const auto key = std::make_tuple(dev, (int)P::FIELD_ID, log_size);
-    auto it = g_lookup.find(key);
-    if (it != g_lookup.end()) {
-        out = it->second;
+    return g_lookup.get(std::make_tuple(dev, (int)P::FIELD_ID, log_size), out, [&](LookupTables& t) {
+        const bool points = log_size > 0;
+        const int log_n4 = points ? log_size + 2 : XS_LO_LOG;
+        const size_t n4 = (size_t)1 << log_n4;
+        std::shared_ptr<const void> plan_hold;  // keeps the plan (and its power table) alive across the launches
+        PLK_TRY(build_domain_tables<P>(log_n4, stream, t, plan_hold));
+        if (points) {
+            PLK_TRY(t.l0.alloc(n4 * 32));
+            ScratchSet ss(stream);
+            void* den = ss.get(n4 * 32);
+            if (!den) return PLK_ERR_OOM;
+            const unsigned blocks = (unsigned)((n4 + 127) / 128);
+            k_lookup_l0_den<P><<<blocks, 128, 0, stream>>>((const uint4*)t.xs_lo.p, (const uint4*)t.xs_hi.p, log_size, (uint4*)den);
+            PLK_HIP_TRY(hipGetLastError());
+            PLK_TRY(field_batch_inverse_dev_impl(P::FIELD_ID, den, t.l0.p, nullptr, nullptr, n4, stream));
+            k_lookup_l0<P><<<blocks, 128, 0, stream>>>((const uint4*)t.xs_lo.p, (const uint4*)t.xs_hi.p, log_size, (uint4*)t.l0.p);
+            PLK_HIP_TRY(hipGetLastError());
+        }
+        PLK_HIP_TRY(hipStreamSynchronize(stream));  // the power table of the plan is only borrowed for these launches
         return PLK_OK;
-    }
-    const void* pw = nullptr;
-    int log_t = 0;
-    std::shared_ptr<const void> plan_hold;  // keeps the plan (and its power table) alive across the launches below
-    PLK_TRY(ntt_plan_pow_table(P::FIELD_ID, (unsigned)log_n4, &pw, &log_t, &plan_hold));
-    auto t = std::make_shared<LookupTables>();
-    const size_t n4 = (size_t)1 << log_n4;
-    const size_t n_lo = (size_t)1 << XS_LO_LOG, n_hi = log_n4 > XS_LO_LOG ? (size_t)1 << (log_n4 - XS_LO_LOG) : 1;
-    PLK_HIP_TRY(hipMalloc(&t->xs_lo, n_lo * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_hi, n_hi * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_lo_z, n_lo * 32));
-    PLK_HIP_TRY(hipMalloc(&t->xs_hi_z, n_hi * 32));
-    PLK_HIP_TRY(hipMalloc(&t->small, 8 * 32));
-    PLK_HIP_TRY(hipMalloc(&t->top, (size_t)LZ_TOP_ROWS * LZ_TOP_STRIDE * 4));
-    const size_t cnt = n_lo + n_hi + 7 + LZ_TOP_ROWS;
-    k_plonk_xs<P><<<(unsigned)((cnt + 127) / 128), 128, 0, stream>>>((const uint4*)pw, log_t, log_n4, (uint4*)t->xs_lo, (uint4*)t->xs_hi, (uint4*)t->xs_lo_z,
-                                                                     (uint4*)t->xs_hi_z, (uint4*)t->small, (uint32_t*)t->top);
-    PLK_HIP_TRY(hipGetLastError());
-    if (points) {
-        PLK_HIP_TRY(hipMalloc(&t->l0, n4 * 32));
-        ScratchSet ss(stream);
-        void* den = ss.get(n4 * 32);
-        if (!den) return PLK_ERR_OOM;
-        const unsigned blocks = (unsigned)((n4 + 127) / 128);
-        k_lookup_l0_den<P><<<blocks, 128, 0, stream>>>((const uint4*)t->xs_lo, (const uint4*)t->xs_hi, log_size, (uint4*)den);
-        PLK_HIP_TRY(hipGetLastError());
-        PLK_TRY(field_batch_inverse_dev_impl(P::FIELD_ID, den, t->l0, nullptr, nullptr, n4, stream));
-        k_lookup_l0<P><<<blocks, 128, 0, stream>>>((const uint4*)t->xs_lo, (const uint4*)t->xs_hi, log_size, (uint4*)t->l0);
-        PLK_HIP_TRY(hipGetLastError());
-    }
-    PLK_HIP_TRY(hipStreamSynchronize(stream));  // the power table of the plan is only borrowed for these launches
-    g_lookup[key] = t;
-    out = t;
-    return PLK_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,7 +266,7 @@ static int grand_product_t(unsigned log_size, const void* d_f, const void* d_t, 
     if (e == hipSuccess) {
         k_lookup_scalars<P><<<1, 64, 0, stream>>>(sc, nullptr, nullptr, 0, scal);
         k_lookup_rows<P><<<(unsigned)tiles, LKP_LANES, 0, stream>>>((const uint4*)d_f, (const uint4*)d_t, (const uint4*)d_s, scal, n, (uint4*)d_out, tile_tot, zeros,
-                                                                    (const uint32_t*)tb->top);
+                                                                    (const uint32_t*)tb->top.p);
         k_perm_tiles<P><<<1, PERM_SCAN_LANES, 0, stream>>>(tile_tot, tiles, zeros, (uint32_t*)d_status);
         k_lookup_fix<P><<<(unsigned)((N + 255) / 256), 256, 0, stream>>>((uint4*)d_out, tile_tot, n);
         e = hipGetLastError();
@@ -384,9 +345,9 @@ static int lookup_points_t(unsigned log_size, const void* d_values, const Lookup
     ScratchSet ss(stream);
     uint32_t* scal = (uint32_t*)ss.get((size_t)LKP_SCALARS * FzCfg<P>::NZ * 4);
     if (!scal) return PLK_ERR_OOM;
-    k_lookup_scalars<P><<<1, 64, 0, stream>>>(sc, (const uint4*)tb->xs_lo_z, (const uint4*)tb->xs_hi_z, n4 - 4, scal);
-    k_lookup_points<P><<<(unsigned)((n4 + 127) / 128), 128, 0, stream>>>((const uint4*)d_values, (const uint4*)tb->xs_lo_z, (const uint4*)tb->xs_hi_z,
-                                                                         (const uint4*)tb->l0, scal, (int)log_size, (uint4*)d_out, (const uint32_t*)tb->top);
+    k_lookup_scalars<P><<<1, 64, 0, stream>>>(sc, (const uint4*)tb->xs_lo_z.p, (const uint4*)tb->xs_hi_z.p, n4 - 4, scal);
+    k_lookup_points<P><<<(unsigned)((n4 + 127) / 128), 128, 0, stream>>>((const uint4*)d_values, (const uint4*)tb->xs_lo_z.p, (const uint4*)tb->xs_hi_z.p,
+                                                                         (const uint4*)tb->l0.p, scal, (int)log_size, (uint4*)d_out, (const uint32_t*)tb->top.p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PLK_ERR_HIP, "plookup vanishing points launch failed: %s", hipGetErrorString(e));
     // the tables stay alive in the cache (plk_ntt_clear_cache / plk_shutdown drop them after a device synchronisation)

@@ -16,9 +16,7 @@
 //
 // Results are the reference's, bit for bit: every output is a fully reduced field element and the
 // reference computes the same field values (its result length, 2^ceil(log2(degree + 1)), included).
-#include <map>
 #include <memory>
-#include <mutex>
 #include <tuple>
 
 #include "common.h"
@@ -77,62 +75,36 @@ template <class P> __global__ void __launch_bounds__(64) k_zh_inv_table(const ui
 }
 
 struct GeomTables {
-    void* lo[2] = {nullptr, nullptr};  // g, g^-1
-    void* hi[2] = {nullptr, nullptr};
-    void* cst = nullptr;
-    ~GeomTables() {
-        for (int d = 0; d < 2; ++d) {
-            if (lo[d]) (void)hipFree(lo[d]);
-            if (hi[d]) (void)hipFree(hi[d]);
-        }
-        if (cst) (void)hipFree(cst);
-    }
+    DevBuf lo[2];  // g, g^-1
+    DevBuf hi[2];
+    DevBuf cst;
 };
 struct ZhTable {
-    void* inv = nullptr;
+    DevBuf inv;
     size_t ord = 0;
-    ~ZhTable() {
-        if (inv) (void)hipFree(inv);
-    }
 };
 
-static std::mutex g_poly_mu;
-static std::map<std::tuple<int, int, int>, std::shared_ptr<GeomTables>> g_geom;          // (device, field, log_size)
-static std::map<std::tuple<int, int, int, uint64_t>, std::shared_ptr<ZhTable>> g_zh;     // (device, field, log_size, n)
 constexpr size_t ZH_CACHE_MAX_ORD = (size_t)1 << 16;  // larger tables are rebuilt per call in scratch memory
 constexpr size_t ZH_CACHE_MAX_ENTRIES = 64;
-
-int poly_clear_cache_impl() {
-    std::lock_guard<std::mutex> lk(g_poly_mu);
-    g_geom.clear();
-    g_zh.clear();
-    return PLK_OK;
-}
+static TableCache<std::tuple<int, int, int>, GeomTables> g_geom;                                  // (device, field, log_size)
+static TableCache<std::tuple<int, int, int, uint64_t>, ZhTable> g_zh(ZH_CACHE_MAX_ENTRIES);       // (device, field, log_size, n)
 
 template <class P> static int get_geom_t(int dev, int log_size, hipStream_t stream, std::shared_ptr<GeomTables>& out) {
-    std::lock_guard<std::mutex> lk(g_poly_mu);
-    const auto key = std::make_tuple(dev, (int)P::FIELD_ID, log_size);
-    auto it = g_geom.find(key);
-    if (it != g_geom.end()) {
-        out = it->second;
+    return g_geom.get(std::make_tuple(dev, (int)P::FIELD_ID, log_size), out, [&](GeomTables& gt) {
+        const size_t n_lo = (size_t)1 << NTT_POW_LO_LOG;
+        const size_t n_hi = log_size > NTT_POW_LO_LOG ? (size_t)1 << (log_size - NTT_POW_LO_LOG) : 1;
+        PLK_TRY(gt.cst.alloc(32));
+        for (int d = 0; d < 2; ++d) {
+            PLK_TRY(gt.lo[d].alloc(n_lo * 32));
+            PLK_TRY(gt.hi[d].alloc(n_hi * 32));
+            k_geom_fill<P><<<(unsigned)((n_lo + n_hi + 127) / 128), 128, 0, stream>>>(d, (uint4*)gt.lo[d].p, (uint4*)gt.hi[d].p, n_hi,
+                                                                                      d == 0 ? (uint4*)gt.cst.p : nullptr);
+            PLK_HIP_TRY(hipGetLastError());
+        }
+        // other streams may pick the tables out of the cache right away
+        PLK_HIP_TRY(hipStreamSynchronize(stream));
         return PLK_OK;
-    }
-    auto gt = std::make_shared<GeomTables>();
-    const size_t n_lo = (size_t)1 << NTT_POW_LO_LOG;
-    const size_t n_hi = log_size > NTT_POW_LO_LOG ? (size_t)1 << (log_size - NTT_POW_LO_LOG) : 1;
-    PLK_HIP_TRY(hipMalloc(&gt->cst, 32));
-    for (int d = 0; d < 2; ++d) {
-        PLK_HIP_TRY(hipMalloc(&gt->lo[d], n_lo * 32));
-        PLK_HIP_TRY(hipMalloc(&gt->hi[d], n_hi * 32));
-        k_geom_fill<P><<<(unsigned)((n_lo + n_hi + 127) / 128), 128, 0, stream>>>(d, (uint4*)gt->lo[d], (uint4*)gt->hi[d], n_hi,
-                                                                                  d == 0 ? (uint4*)gt->cst : nullptr);
-        PLK_HIP_TRY(hipGetLastError());
-    }
-    // other streams may pick the tables out of the cache right away
-    PLK_HIP_TRY(hipStreamSynchronize(stream));
-    g_geom[key] = gt;
-    out = gt;
-    return PLK_OK;
+    });
 }
 
 static int read_degrees(const void* const* d_polys, const size_t* lens, int count, size_t* deg_plus_one, hipStream_t stream) {
@@ -199,22 +171,15 @@ static int divide_by_z_h_t(const void* d_coeffs, size_t len, uint64_t n, void* d
     void* zh_scratch = nullptr;
     const void* inv_tab = nullptr;
     if (ord <= ZH_CACHE_MAX_ORD) {
-        std::lock_guard<std::mutex> lk(g_poly_mu);
-        const auto key = std::make_tuple(dev, (int)P::FIELD_ID, log_size, n);
-        auto it = g_zh.find(key);
-        if (it != g_zh.end()) {
-            zh = it->second;
-        } else {
-            zh = std::make_shared<ZhTable>();
-            zh->ord = ord;
-            PLK_HIP_TRY(hipMalloc(&zh->inv, ord * 32));
-            k_zh_inv_table<P><<<(unsigned)((ord + 63) / 64), 64, 0, stream>>>((const uint4*)pw, log_t, log_size, n, ord, (uint4*)zh->inv);
+        PLK_TRY(g_zh.get(std::make_tuple(dev, (int)P::FIELD_ID, log_size, (uint64_t)n), zh, [&](ZhTable& t) {
+            t.ord = ord;
+            PLK_TRY(t.inv.alloc(ord * 32));
+            k_zh_inv_table<P><<<(unsigned)((ord + 63) / 64), 64, 0, stream>>>((const uint4*)pw, log_t, log_size, n, ord, (uint4*)t.inv.p);
             PLK_HIP_TRY(hipGetLastError());
             PLK_HIP_TRY(hipStreamSynchronize(stream));
-            if (g_zh.size() >= ZH_CACHE_MAX_ENTRIES) g_zh.erase(g_zh.begin());
-            g_zh[key] = zh;
-        }
-        inv_tab = zh->inv;
+            return PLK_OK;
+        }));
+        inv_tab = zh->inv.p;
     } else {
         zh_scratch = scratch_acquire(ord * 32, stream);
         if (!zh_scratch) return PLK_ERR_OOM;
@@ -226,8 +191,8 @@ static int divide_by_z_h_t(const void* d_coeffs, size_t len, uint64_t n, void* d
     NttHooks fw;
     fw.in_len = dp1;
     fw.in_stride = dp1;
-    fw.in_lo = gt->lo[0];
-    fw.in_hi = gt->hi[0];
+    fw.in_lo = gt->lo[0].p;
+    fw.in_hi = gt->hi[0].p;
     fw.out_tab = inv_tab;
     fw.out_mask = ord - 1;
     int rc = ntt_dev_hooked_impl(P::FIELD_ID, (unsigned)log_size, 0, 1, d_coeffs, d_out, fw, stream);
@@ -236,8 +201,8 @@ static int divide_by_z_h_t(const void* d_coeffs, size_t len, uint64_t n, void* d
         NttHooks bw;
         bw.in_len = size;
         bw.in_stride = size;
-        bw.out_lo = gt->lo[1];
-        bw.out_hi = gt->hi[1];
+        bw.out_lo = gt->lo[1].p;
+        bw.out_hi = gt->hi[1].p;
         rc = ntt_dev_hooked_impl(P::FIELD_ID, (unsigned)log_size, 1, 1, d_out, d_out, bw, stream);
     }
     if (zh_scratch) scratch_release(zh_scratch, stream);
@@ -285,7 +250,7 @@ static int poly_mul_t(const void* d_a, size_t la, const void* d_b, size_t lb, vo
     NttHooks ha;
     ha.in_len = dp1[0];
     ha.in_stride = dp1[0];
-    ha.out_tab = gt->cst;
+    ha.out_tab = gt->cst.p;
     ha.out_mask = 0;
     int rc = ntt_dev_hooked_impl(P::FIELD_ID, (unsigned)log_size, 0, 1, d_a, ev_a, ha, stream);
     if (rc == PLK_OK) {
