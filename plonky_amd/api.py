@@ -68,6 +68,12 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _u64(x, *shape):
+    """host limbs as a contiguous uint64 array, of that shape when one is given"""
+    a = np.ascontiguousarray(x, dtype=np.uint64)
+    return a.reshape(*shape) if shape else a
+
+
 def _elems(field, a):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     L = _FIELD_LIMBS[field]
@@ -506,11 +512,10 @@ def curve_op(curve, op, a, b=None, flags=None, param=0):
     flags (n,) or None, lambdas (n, L)).  Returns (affine results (m, 2, L), zero flags (m,), mismatch word); m = ceil(n / param) for
     "wave_sum_q", n otherwise."""
     L = _CURVE_LIMBS[curve]
-    u64 = lambda x, *shape: np.ascontiguousarray(x, dtype=np.uint64).reshape(*shape)
     u8 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
-    axy, az, al = u64(a[0], -1, 2, L), u8(a[1]), u64(a[2], -1, L)
+    axy, az, al = _u64(a[0], -1, 2, L), u8(a[1]), _u64(a[2], -1, L)
     n = axy.shape[0]
-    bxy, bz, bl = (None, None, None) if b is None else (u64(b[0], n, 2, L), u8(b[1]), None if b[2] is None else u64(b[2], n, L))
+    bxy, bz, bl = (None, None, None) if b is None else (_u64(b[0], n, 2, L), u8(b[1]), None if b[2] is None else _u64(b[2], n, L))
     fl = np.zeros(n, dtype=np.uint8) if flags is None else u8(flags)
     code = CURVE_OPS[op]
     m = -(-n // param) if code == 7 else n

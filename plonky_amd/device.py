@@ -4,16 +4,60 @@ PyTorch is plumbing here: it owns device memory and streams; every computation i
 libplonky_hip.so.  Tensors are int64 views of the reference's u64 limbs, shape (..., L).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
 
-from . import lib as _lib
-from .api import _CURVE_LIMBS, _FIELD_LIMBS, MsmPrecomputation, log2_strict
+from . import api as _api, lib as _lib
+from .api import _CURVE_LIMBS, _FIELD_LIMBS, MsmPrecomputation, _ptr as _hp, _u64, log2_strict
 
 
+# ---- the marshalling layer: every wrapper below is a check, _out_tensor and one call ----
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dp(t):
+    """the device pointer of a tensor; None for None"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _dps(tensors, count):
+    """a ctypes array of `count` device pointers (None: a null entry)"""
+    return (ctypes.c_void_p * count)(*map(_dp, tensors))
+
+
+def _check(t, dtype=torch.int64, shape=None, last=None, numel=None):
+    """The one tensor check: on the device, contiguous, of that dtype (None: not looked at) and, where given, of that shape (a None
+    extent is free), with those trailing extents, of that many elements."""
+    assert t.is_cuda and t.is_contiguous() and (dtype is None or t.dtype == dtype)
+    assert shape is None or (t.dim() == len(shape) and all(w is None or w == s for w, s in zip(shape, t.shape)))
+    assert last is None or tuple(t.shape[-len(last):]) == tuple(last)
+    assert numel is None or t.numel() == numel
+
+
+def _out_tensor(out, shape, device, dtype=torch.int64, check="shape"):
+    """An `out=` parameter: a fresh tensor when None; the caller's is checked for its exact shape, for its numel alone
+    (check="numel") or not at all (check=None: the wrappers that take it as it is)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if check == "shape":
+        _check(out, dtype, shape=shape)
+    elif check == "numel":
+        _check(out, dtype, numel=math.prod(shape))
+    return out
+
+
+def _status(status, words, device):
+    """A `status=` parameter: None or False - no status words; True - a fresh tensor; or the caller's int32 tensor of exactly `words`
+    -> (the tensor or None, its pointer or None)."""
+    if status is None or status is False:
+        return None, None
+    if status is True:
+        status = torch.empty(words, dtype=torch.int32, device=device)
+    _check(status, torch.int32, numel=words)
+    return status, _dp(status)
 
 
 def init(device_index=None):
@@ -25,8 +69,7 @@ def init(device_index=None):
 
 
 def to_device(arr, device="cuda"):
-    a = np.ascontiguousarray(arr, dtype=np.uint64)
-    return torch.from_numpy(a.view(np.int64)).to(device)
+    return torch.from_numpy(_u64(arr).view(np.int64)).to(device)
 
 
 def to_host(t):
@@ -35,16 +78,13 @@ def to_host(t):
 
 def ntt_dev(field, x, inverse=False, out=None):
     """x: (batch, n, L) or (n, L) int64 CUDA tensor, L = 4 (6 for Bls12377Base); returns the transforms (natural order)."""
-    assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous()
     L = _FIELD_LIMBS[field]
-    assert x.shape[-1] == L
+    _check(x, last=(L,))
     n = x.shape[-2]
     batch = x.numel() // (n * L)
     log_n = log2_strict(n)
-    if out is None:
-        out = torch.empty_like(x)
-    _lib.check(_lib.load().plk_ntt_dev(field, log_n, 1 if inverse else 0, batch, ctypes.c_void_p(x.data_ptr()),
-                                       ctypes.c_void_p(out.data_ptr()), _stream()))
+    out = _out_tensor(out, x.shape, x.device, check=None)
+    _lib.check(_lib.load().plk_ntt_dev(field, log_n, 1 if inverse else 0, batch, _dp(x), _dp(out), _stream()))
     return out
 
 
@@ -52,54 +92,42 @@ def ntt_padded_dev(field, x, log_n, out=None):
     """polynomials_to_values_padded on device-resident coefficients: x (batch, len, 4) or (len, 4) with
     len <= 2^log_n; returns (batch, 2^log_n, 4) evaluations.  The zero padding is never stored.  (6 limbs for Bls12377Base.)"""
     L = _FIELD_LIMBS[field]
-    assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.shape[-1] == L
-    import math
+    _check(x, last=(L,))
     length = x.shape[-2]
     batch = math.prod(x.shape[:-2])  # independent of the length: (B, 0, 4) is B zero polynomials, every output is written
-    n = 1 << log_n
-    shape = x.shape[:-2] + (n, L)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int64, device=x.device)
-    _lib.check(_lib.load().plk_ntt_padded_dev(field, log_n, batch, ctypes.c_void_p(x.data_ptr()), length, length,
-                                              ctypes.c_void_p(out.data_ptr()), _stream()))
+    out = _out_tensor(out, x.shape[:-2] + (1 << log_n, L), x.device, check=None)
+    _lib.check(_lib.load().plk_ntt_padded_dev(field, log_n, batch, _dp(x), length, length, _dp(out), _stream()))
     return out
 
 
 def divide_by_z_h_dev(field, coeffs, n, out=None):
     """Polynomial::divide_by_z_h on a device-resident (len, 4) coefficient tensor; returns a view of the
     2^ceil(log2(degree + 1)) result coefficients (one stream synchronisation: the degree picks the domain)."""
-    assert coeffs.is_cuda and coeffs.dtype == torch.int64 and coeffs.is_contiguous() and coeffs.shape[-1] == 4
+    _check(coeffs, last=(4,))
     length = coeffs.shape[0]
     cap = max(length, 1 << max(0, (length - 1).bit_length()))
-    if out is None:
-        out = torch.empty((cap, 4), dtype=torch.int64, device=coeffs.device)
+    out = _out_tensor(out, (cap, 4), coeffs.device, check=None)
     assert out.shape[0] >= cap
     out_len = ctypes.c_size_t(0)
-    _lib.check(_lib.load().plk_poly_divide_by_z_h_dev(field, ctypes.c_void_p(coeffs.data_ptr()), length, n,
-                                                      ctypes.c_void_p(out.data_ptr()), out.shape[0], ctypes.byref(out_len), _stream()))
+    _lib.check(_lib.load().plk_poly_divide_by_z_h_dev(field, _dp(coeffs), length, n, _dp(out), out.shape[0], ctypes.byref(out_len), _stream()))
     return out[: out_len.value]
 
 
 def poly_mul_dev(field, a, b):
     """Polynomial::mul on device-resident coefficient tensors."""
     for t in (a, b):
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.shape[-1] == 4
+        _check(t, last=(4,))
     cap = 1 << max(0, (a.shape[0] + b.shape[0] - 1).bit_length())
     out = torch.empty((cap, 4), dtype=torch.int64, device=a.device)
     out_len = ctypes.c_size_t(0)
-    _lib.check(_lib.load().plk_poly_mul_dev(field, ctypes.c_void_p(a.data_ptr()), a.shape[0], ctypes.c_void_p(b.data_ptr()), b.shape[0],
-                                            ctypes.c_void_p(out.data_ptr()), cap, ctypes.byref(out_len), _stream()))
+    _lib.check(_lib.load().plk_poly_mul_dev(field, _dp(a), a.shape[0], _dp(b), b.shape[0], _dp(out), cap, ctypes.byref(out_len), _stream()))
     return out[: out_len.value]
 
 
 def gen_bases_dev(curve, n, g0_xy, d_xy, first=0, device="cuda"):
     """B_i = G0 + (first + i) D on the device: (n, 2, L) int64 tensor."""
-    L = _CURVE_LIMBS[curve]
-    out = torch.empty((n, 2, L), dtype=torch.int64, device=device)
-    g0 = np.ascontiguousarray(g0_xy, dtype=np.uint64)
-    d = np.ascontiguousarray(d_xy, dtype=np.uint64)
-    _lib.check(_lib.load().plk_curve_gen_bases_dev(curve, n, first, g0.ctypes.data_as(ctypes.c_void_p), d.ctypes.data_as(ctypes.c_void_p),
-                                                   ctypes.c_void_p(out.data_ptr()), _stream()))
+    out = torch.empty((n, 2, _CURVE_LIMBS[curve]), dtype=torch.int64, device=device)
+    _lib.check(_lib.load().plk_curve_gen_bases_dev(curve, n, first, _hp(_u64(g0_xy)), _hp(_u64(d_xy)), _dp(out), _stream()))
     return out
 
 
@@ -109,48 +137,39 @@ def hash_to_curve_dev(curve, count, seed_start=0, seeds=None, out=None, device="
     msm_precompute_dev takes as it is."""
     L = _CURVE_LIMBS[curve]
     if seeds is not None:
-        assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.shape == (count, L)
+        _check(seeds, shape=(count, L))
         device = seeds.device
-    if out is None:
-        out = torch.empty((count, 2, L), dtype=torch.int64, device=device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
+    out = _out_tensor(out, (count, 2, L), device)
+    assert out.is_cuda  # a fresh one too: `device` is the caller's word
     if seeds is None:
-        _lib.check(_lib.load().plk_hash_to_curve_dev(count, curve, int(seed_start), ctypes.c_void_p(out.data_ptr()), _stream()))
+        _lib.check(_lib.load().plk_hash_to_curve_dev(count, curve, int(seed_start), _dp(out), _stream()))
     else:
-        _lib.check(_lib.load().plk_hash_field_to_curve_dev(count, curve, ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+        _lib.check(_lib.load().plk_hash_field_to_curve_dev(count, curve, _dp(seeds), _dp(out), _stream()))
     return out
 
 
 def msm_precompute_dev(curve, bases, w=11, zero=None, device_window=0, table_free=False):
     """bases: (n, 2, L) int64 CUDA tensor.  table_free: no window tables (generators used once or a few times)."""
-    assert bases.is_cuda and bases.dtype == torch.int64 and bases.is_contiguous()
+    _check(bases)
     n = bases.shape[0]
     ctx = ctypes.c_void_p()
-    zp = ctypes.c_void_p(zero.data_ptr()) if zero is not None else None
-    _lib.check(_lib.load().plk_msm_precompute_dev_ex(curve, n, ctypes.c_void_p(bases.data_ptr()), zp, device_window, 1 if table_free else 0,
-                                                     _stream(), ctypes.byref(ctx)))
+    _lib.check(_lib.load().plk_msm_precompute_dev_ex(curve, n, _dp(bases), _dp(zero), device_window, 1 if table_free else 0, _stream(), ctypes.byref(ctx)))
     return MsmPrecomputation(curve, ctx, n, w)
 
 
 def msm_execute_dev(pre, scalars, out_xy=None, out_zero=None, projective=False):
     """scalars: (batch, n, 4) or (n, 4) int64 CUDA tensor.  Returns (out_xy (batch, 2, L), out_zero (batch,)) on device.
     projective: the reference's own return type - ProjectivePoints x | y | z, not normalised ((batch, 3, L); plk_msm_execute_projective_dev)."""
-    assert scalars.is_cuda and scalars.dtype == torch.int64 and scalars.is_contiguous()
+    _check(scalars)
     n = scalars.shape[-2]
     assert n == pre.n, "powers_per_generator.len() != scalars.len()"
     batch = scalars.numel() // (n * 4) if n else 1
     L = _CURVE_LIMBS[pre.curve]
-    if out_xy is None:
-        out_xy = torch.empty((batch, 3 if projective else 2, L), dtype=torch.int64, device=scalars.device)
-    if out_zero is None:
-        out_zero = torch.empty((batch,), dtype=torch.uint8, device=scalars.device)
-    if projective:
-        assert out_xy.numel() == batch * 3 * L
-        _lib.check(_lib.load().plk_msm_execute_projective_dev(pre._ctx, batch, ctypes.c_void_p(scalars.data_ptr()), n, ctypes.c_void_p(out_xy.data_ptr()),
-                                                              ctypes.c_void_p(out_zero.data_ptr()), _stream()))
-        return out_xy, out_zero
-    _lib.check(_lib.load().plk_msm_execute_dev(pre._ctx, batch, ctypes.c_void_p(scalars.data_ptr()), n, ctypes.c_void_p(out_xy.data_ptr()),
-                                               ctypes.c_void_p(out_zero.data_ptr()), _stream()))
+    out_xy = _out_tensor(out_xy, (batch, 3 if projective else 2, L), scalars.device, check=None)
+    out_zero = _out_tensor(out_zero, (batch,), scalars.device, torch.uint8, check=None)
+    assert not projective or out_xy.numel() == batch * 3 * L
+    execute = _lib.load().plk_msm_execute_projective_dev if projective else _lib.load().plk_msm_execute_dev
+    _lib.check(execute(pre._ctx, batch, _dp(scalars), n, _dp(out_xy), _dp(out_zero), _stream()))
     return out_xy, out_zero
 
 
@@ -160,27 +179,22 @@ def msm_execute_parts_dev(pre, parts, out_xy=None, out_zero=None, buckets=None):
     buckets (optional): [(part, parts)] per vector - the vector keeps only the part-th of `parts` ranges of the coarse bucket bins
     (plk_msm_execute_parts_buckets_dev: a rank's BUCKET share of a sharded vector; (0, 1): every bucket)."""
     batch = len(parts)
-    L = _CURVE_LIMBS[pre.curve]
     dev0 = parts[0][1].device
-    if out_xy is None:
-        out_xy = torch.empty((batch, 2, L), dtype=torch.int64, device=dev0)
-    if out_zero is None:
-        out_zero = torch.empty((batch,), dtype=torch.uint8, device=dev0)
+    out_xy = _out_tensor(out_xy, (batch, 2, _CURVE_LIMBS[pre.curve]), dev0, check=None)
+    out_zero = _out_tensor(out_zero, (batch,), dev0, torch.uint8, check=None)
     first = np.array([p[0] for p in parts], dtype=np.uint64)
     count = np.array([p[1].shape[0] for p in parts], dtype=np.uint64)
     for _, t in parts:
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.shape[-1] == 4
-    ptrs = (ctypes.c_void_p * batch)(*[p[1].data_ptr() for p in parts])
+        _check(t, last=(4,))
+    args = [pre._ctx, batch, _hp(first), _hp(count), _dps([p[1] for p in parts], batch)]
+    execute = _lib.load().plk_msm_execute_parts_dev
     if buckets is not None:
         assert len(buckets) == batch
         bp = np.array([b[0] for b in buckets], dtype=np.uint32)
         bn = np.array([b[1] for b in buckets], dtype=np.uint32)
-        _lib.check(_lib.load().plk_msm_execute_parts_buckets_dev(pre._ctx, batch, first.ctypes.data_as(ctypes.c_void_p), count.ctypes.data_as(ctypes.c_void_p),
-                                                                 ptrs, bp.ctypes.data_as(ctypes.c_void_p), bn.ctypes.data_as(ctypes.c_void_p),
-                                                                 ctypes.c_void_p(out_xy.data_ptr()), ctypes.c_void_p(out_zero.data_ptr()), _stream()))
-        return out_xy, out_zero
-    _lib.check(_lib.load().plk_msm_execute_parts_dev(pre._ctx, batch, first.ctypes.data_as(ctypes.c_void_p), count.ctypes.data_as(ctypes.c_void_p), ptrs,
-                                                     ctypes.c_void_p(out_xy.data_ptr()), ctypes.c_void_p(out_zero.data_ptr()), _stream()))
+        args += [_hp(bp), _hp(bn)]
+        execute = _lib.load().plk_msm_execute_parts_buckets_dev
+    _lib.check(execute(*args, _dp(out_xy), _dp(out_zero), _stream()))
     return out_xy, out_zero
 
 
@@ -189,17 +203,13 @@ def vanishing_points_dev(field, log_degree, constants_8n, wire_values_8n, s_sigm
     """Prover::vanishing_poly's 8n-point loop (plonk.rs:392-453) on device-resident tables: int64 CUDA tensors (6, 8n, 4),
     (9, 8n, 4), (6, 8n, 4), (8n, 4); the scalars are host arrays (4 limbs each; k_is (6, 4))."""
     n8 = 8 << log_degree
-    for t, rows in ((constants_8n, 6), (wire_values_8n, 9), (s_sigma_values_8n, 6), (plonk_z_points_8n, 1)):
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == rows * n8 * 4
-    if out is None:
-        out = torch.empty((n8, 4), dtype=torch.int64, device=constants_8n.device)
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(6, 4)
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma, inner_zeta, inner_a)]
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(_lib.load().plk_plonk_vanishing_points_dev(field, log_degree, ctypes.c_void_p(constants_8n.data_ptr()),
-                                                          ctypes.c_void_p(wire_values_8n.data_ptr()), ctypes.c_void_p(s_sigma_values_8n.data_ptr()),
-                                                          ctypes.c_void_p(plonk_z_points_8n.data_ptr()), p(ks), *[p(x) for x in sc],
-                                                          ctypes.c_void_p(out.data_ptr()), _stream()))
+    tables = ((constants_8n, 6), (wire_values_8n, 9), (s_sigma_values_8n, 6), (plonk_z_points_8n, 1))
+    for t, rows in tables:
+        _check(t, numel=rows * n8 * 4)
+    out = _out_tensor(out, (n8, 4), constants_8n.device, check=None)
+    sc = [_u64(x, 4) for x in (alpha, beta, gamma, inner_zeta, inner_a)]
+    _lib.check(_lib.load().plk_plonk_vanishing_points_dev(field, log_degree, *[_dp(t) for t, _ in tables], _hp(_u64(k_is, 6, 4)), *map(_hp, sc),
+                                                          _dp(out), _stream()))
     return out
 
 
@@ -209,25 +219,15 @@ def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k
     (k_is (6, 4)).  Returns Z (n, 4); with status=True (or a (2,) int32 CUDA tensor) also the status words, written in stream
     order: [0] zero denominators among rows 0..n-2 (Z unspecified when > 0), [1] 1 iff Z closes the cycle."""
     n = 1 << log_degree
-    assert wire_values.is_cuda and wire_values.dtype == torch.int64 and wire_values.is_contiguous()
+    _check(wire_values)
     assert wire_values.numel() >= 6 * n * 4 and wire_values.numel() % (n * 4) == 0
-    assert s_sigma_values.is_cuda and s_sigma_values.dtype == torch.int64 and s_sigma_values.is_contiguous()
-    assert s_sigma_values.numel() == 6 * n * sigma_stride * 4
-    if out is None:
-        out = torch.empty((n, 4), dtype=torch.int64, device=wire_values.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == n * 4
-    want_status = status is not None and status is not False
-    if status is True:
-        status = torch.empty(2, dtype=torch.int32, device=wire_values.device)
-    if want_status:
-        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(6, 4)
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma)]
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(_lib.load().plk_plonk_permutation_z_dev(field, log_degree, ctypes.c_void_p(wire_values.data_ptr()), ctypes.c_void_p(s_sigma_values.data_ptr()),
-                                                       sigma_stride, p(ks), *[p(x) for x in sc], ctypes.c_void_p(out.data_ptr()),
-                                                       ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
-    return (out, status) if want_status else out
+    _check(s_sigma_values, numel=6 * n * sigma_stride * 4)
+    out = _out_tensor(out, (n, 4), wire_values.device, check="numel")
+    status, sp = _status(status, 2, wire_values.device)
+    ks, b, g = _u64(k_is, 6, 4), _u64(beta, 4), _u64(gamma, 4)
+    _lib.check(_lib.load().plk_plonk_permutation_z_dev(field, log_degree, _dp(wire_values), _dp(s_sigma_values), sigma_stride, _hp(ks), _hp(b), _hp(g),
+                                                       _dp(out), sp, _stream()))
+    return out if status is None else (out, status)
 
 
 # ---- the copy-constraint permutation and the setup-time half of CircuitBuilder::build ----
@@ -240,21 +240,15 @@ def sigma_dev(field, log_degree, members, offsets, k_is, want_sigma=True, status
     (the outputs are unspecified when one is nonzero)."""
     n = 1 << log_degree
     for t in (members, offsets):
-        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1
+        _check(t, torch.int32, shape=(None,))
     assert offsets.numel() >= 1
     sigma = torch.empty(6 * n, dtype=torch.int32, device=members.device) if want_sigma else None
     values = torch.empty((6, n, 4), dtype=torch.int64, device=members.device)
-    want_status = status is not None and status is not False
-    if status is True:
-        status = torch.empty(3, dtype=torch.int32, device=members.device)
-    if want_status:
-        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 3
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(6, 4)
-    _lib.check(_lib.load().plk_plonk_sigma_dev(log_degree, field, ctypes.c_void_p(members.data_ptr() if members.numel() else None),
-                                               ctypes.c_void_p(offsets.data_ptr()), offsets.numel() - 1, members.numel(), ks.ctypes.data_as(ctypes.c_void_p),
-                                               ctypes.c_void_p(sigma.data_ptr() if want_sigma else None), ctypes.c_void_p(values.data_ptr()),
-                                               ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
-    return (sigma, values, status) if want_status else (sigma, values)
+    status, sp = _status(status, 3, members.device)
+    ks = _u64(k_is, 6, 4)
+    _lib.check(_lib.load().plk_plonk_sigma_dev(log_degree, field, _dp(members if members.numel() else None), _dp(offsets), offsets.numel() - 1,
+                                               members.numel(), _hp(ks), _dp(sigma), _dp(values), sp, _stream()))
+    return (sigma, values) if status is None else (sigma, values, status)
 
 
 class CircuitKey:
@@ -273,10 +267,9 @@ def circuit_key_dev(curve, log_degree, gate_constants, members, offsets, k_is, w
       constant_polynomials (6, n, 4), constants_8n (6, 8n, 4), c_constants ((6, 2, L), (6,) zero flags)
       sigma (6n,), s_sigma_polynomials (6, n, 4), s_sigma_values_8n (6, 8n, 4), c_s_sigmas ((6, 2, L), (6,))
     The commitments are unblinded (plonk_util.rs:215-231 with blinding off): the scalar of pedersen_h is zero."""
-    from .api import CURVE_SCALAR_FIELD
-    field = CURVE_SCALAR_FIELD[curve]
+    field = _api.CURVE_SCALAR_FIELD[curve]
     n = 1 << log_degree
-    assert gate_constants.is_cuda and gate_constants.dtype == torch.int64 and tuple(gate_constants.shape) == (n, 6, 4)
+    assert gate_constants.is_cuda and gate_constants.dtype == torch.int64 and tuple(gate_constants.shape) == (n, 6, 4)  # any strides: transposed below
     gens = hash_to_curve_dev(curve, n + 2, device=gate_constants.device)
     pre = msm_precompute_dev(curve, gens[: n + 1], w=w)
 
@@ -304,35 +297,22 @@ def plookup_grand_polynomial_dev(field, log_size, f, t, s, beta, gamma, out=None
     over all n rows is 1."""
     size = 1 << log_size
     for x, rows in ((f, size), (t, size), (s, 2 * size - 1)):
-        assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.numel() == rows * 4
-    if out is None:
-        out = torch.empty((size, 4), dtype=torch.int64, device=f.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == size * 4
-    want_status = status is not None and status is not False
-    if status is True:
-        status = torch.empty(2, dtype=torch.int32, device=f.device)
-    if want_status:
-        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma)]
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(_lib.load().plk_plookup_grand_product_dev(log_size, field, ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                                                         ctypes.c_void_p(s.data_ptr()), *[p(x) for x in sc], ctypes.c_void_p(out.data_ptr()),
-                                                         ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
-    return (out, status) if want_status else out
+        _check(x, numel=rows * 4)
+    out = _out_tensor(out, (size, 4), f.device, check="numel")
+    status, sp = _status(status, 2, f.device)
+    b, g = _u64(beta, 4), _u64(gamma, 4)
+    _lib.check(_lib.load().plk_plookup_grand_product_dev(log_size, field, _dp(f), _dp(t), _dp(s), _hp(b), _hp(g), _dp(out), sp, _stream()))
+    return out if status is None else (out, status)
 
 
 def plookup_vanishing_values_dev(field, log_size, values_4n, alpha, beta, gamma, out=None):
     """The 4N-point loop of vanishing_polynomial (plookup.rs:225-269): values_4n an int64 CUDA tensor (5, 4 N, 4), rows z, f, t, h1, h2
     (ntt_padded_dev to log_size + 2); the scalars are host limbs.  Returns (4 N, 4)."""
     n4 = 4 << log_size
-    assert values_4n.is_cuda and values_4n.dtype == torch.int64 and values_4n.is_contiguous() and values_4n.numel() == 5 * n4 * 4
-    if out is None:
-        out = torch.empty((n4, 4), dtype=torch.int64, device=values_4n.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == n4 * 4
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma)]
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(_lib.load().plk_plookup_vanishing_points_dev(log_size, field, ctypes.c_void_p(values_4n.data_ptr()), *[p(x) for x in sc],
-                                                            ctypes.c_void_p(out.data_ptr()), _stream()))
+    _check(values_4n, numel=5 * n4 * 4)
+    out = _out_tensor(out, (n4, 4), values_4n.device, check="numel")
+    sc = [_u64(x, 4) for x in (alpha, beta, gamma)]
+    _lib.check(_lib.load().plk_plookup_vanishing_points_dev(log_size, field, _dp(values_4n), *map(_hp, sc), _dp(out), _stream()))
     return out
 
 
@@ -343,43 +323,25 @@ def plookup_sorted_multiset_dev(field, log_size, f, t, out=None, status=False):
     panics; the rows of s beyond the total are zero then), [1] distinct values in t."""
     size = 1 << log_size
     for x in (f, t):
-        assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.numel() == size * 4
-    if out is None:
-        out = torch.empty((2 * size - 1, 4), dtype=torch.int64, device=f.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == (2 * size - 1) * 4
-    want_status = status is not None and status is not False
-    if status is True:
-        status = torch.empty(2, dtype=torch.int32, device=f.device)
-    if want_status:
-        assert status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == 2
-    _lib.check(_lib.load().plk_plookup_sorted_multiset_dev(log_size, field, ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                                                           ctypes.c_void_p(out.data_ptr()),
-                                                           ctypes.c_void_p(status.data_ptr() if want_status else None), _stream()))
-    return (out, status) if want_status else out
+        _check(x, numel=size * 4)
+    out = _out_tensor(out, (2 * size - 1, 4), f.device, check="numel")
+    status, sp = _status(status, 2, f.device)
+    _lib.check(_lib.load().plk_plookup_sorted_multiset_dev(log_size, field, _dp(f), _dp(t), _dp(out), sp, _stream()))
+    return out if status is None else (out, status)
 
 
 # ---- the opening step on device-resident polynomials (plonk.rs:261-308, halo.rs:38-44, 143-155) ----
 def _poly_list(polys):
     """list of (len, 4) int64 CUDA tensors -> (ctypes array of device pointers, size_t lengths)"""
     for t in polys:
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4
-    ptrs = (ctypes.c_void_p * max(1, len(polys)))(*[t.data_ptr() if t.shape[0] else None for t in polys])
-    lens = np.array([t.shape[0] for t in polys], dtype=np.uint64)
-    return ptrs, lens
-
-
-def _out_tensor(out, shape, device):
-    if out is None:
-        return torch.empty(shape, dtype=torch.int64, device=device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == tuple(shape)
-    return out
+        _check(t, shape=(None, 4))
+    return _dps([t if t.shape[0] else None for t in polys], max(1, len(polys))), np.array([t.shape[0] for t in polys], dtype=np.uint64)
 
 
 def powers_dev(field, x, n, out=None, device="cuda"):
     """powers (plonk_util.rs:123-133) -> (n, 4) int64 CUDA tensor; x: host limbs."""
     out = _out_tensor(out, (n, 4), device)
-    xs = _limbs(x)
-    _lib.check(_lib.load().plk_field_powers_dev(field, xs.ctypes.data_as(ctypes.c_void_p), n, ctypes.c_void_p(out.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_field_powers_dev(field, _hp(_u64(x, 4)), n, _dp(out), _stream()))
     return out
 
 
@@ -388,41 +350,35 @@ def eval_polys_dev(field, polys, points, out=None):
     same tensor may appear twice), points (n_points, 4) host limbs, 1..8 points -> (n_points, n_polys, 4) CUDA tensor.  Every
     polynomial is read once."""
     ptrs, lens = _poly_list(polys)
-    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
-    device = polys[0].device if polys else "cuda"
-    out = _out_tensor(out, (pts.shape[0], len(polys), 4), device)
-    _lib.check(_lib.load().plk_plonk_eval_polys_dev(field, len(polys), ptrs, lens.ctypes.data_as(ctypes.c_void_p), pts.shape[0],
-                                                    pts.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), _stream()))
+    pts = _u64(points, -1, 4)
+    out = _out_tensor(out, (pts.shape[0], len(polys), 4), polys[0].device if polys else "cuda")
+    _lib.check(_lib.load().plk_plonk_eval_polys_dev(field, len(polys), ptrs, _hp(lens), pts.shape[0], _hp(pts), _dp(out), _stream()))
     return out
 
 
 def reduce_polynomials_dev(field, polys, scalars, degree, out=None):
     """reduced_coeffs (halo.rs:38-44), the argument's halo_a: sum_i scalars[i] * polys[i], zero-padded to `degree` -> (degree, 4)."""
     ptrs, lens = _poly_list(polys)
-    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    sc = _u64(scalars, -1, 4)
     assert sc.shape[0] == len(polys), "one scalar per polynomial"
-    device = polys[0].device if polys else "cuda"
-    out = _out_tensor(out, (degree, 4), device)
-    _lib.check(_lib.load().plk_poly_reduce_dev(field, len(polys), ptrs, lens.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p), degree,
-                                               ctypes.c_void_p(out.data_ptr()), _stream()))
+    out = _out_tensor(out, (degree, 4), polys[0].device if polys else "cuda")
+    _lib.check(_lib.load().plk_poly_reduce_dev(field, len(polys), ptrs, _hp(lens), _hp(sc), degree, _dp(out), _stream()))
     return out
 
 
 def build_halo_b_dev(field, points, v, degree, out=None, device="cuda"):
     """build_halo_b (halo.rs:143-155), the argument's halo_b: out[j] = sum_k v^k points[k]^j -> (degree, 4)."""
-    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
-    vs = _limbs(v)
+    pts, vs = _u64(points, -1, 4), _u64(v, 4)
     out = _out_tensor(out, (degree, 4), device)
-    _lib.check(_lib.load().plk_halo_build_b_dev(field, pts.shape[0], pts.ctypes.data_as(ctypes.c_void_p), vs.ctypes.data_as(ctypes.c_void_p), degree,
-                                                ctypes.c_void_p(out.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_halo_build_b_dev(field, pts.shape[0], _hp(pts), _hp(vs), degree, _dp(out), _stream()))
     return out
 
 
 def halo_s_dev(field, us, out=None, device="cuda"):
     """halo_s (plonk_util.rs:311-326) -> (2^k, 4); us: (k, 4) host limbs, none of them zero."""
-    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    u = _u64(us, -1, 4)
     out = _out_tensor(out, (1 << u.shape[0], 4), device)
-    _lib.check(_lib.load().plk_halo_s_dev(field, u.shape[0], u.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_halo_s_dev(field, u.shape[0], _hp(u), _dp(out), _stream()))
     return out
 
 
@@ -430,33 +386,32 @@ def halo_s_dev(field, us, out=None, device="cuda"):
 def polynomial_division_dev(field, a, b, q_len=None, out=None, rem=None):
     """plk_poly_division_dev: a (la, 4) int64 CUDA tensor, b (lb, 4) host limbs with b[lb - 1] != 0 and 1 <= lb - 1 <= 32 < la ->
     (q, rem): q (q_len, 4), the quotient followed by zeros (q_len defaults to la - k), rem (k, 4).  Nothing is synchronised."""
-    assert a.is_cuda and a.dtype == torch.int64 and a.is_contiguous() and a.dim() == 2 and a.shape[1] == 4
-    bs = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+    _check(a, shape=(None, 4))
+    bs = _u64(b, -1, 4)
     la, k = a.shape[0], bs.shape[0] - 1
     if q_len is None:
         q_len = out.shape[0] if out is not None else max(la - k, 0)
     out = _out_tensor(out, (q_len, 4), a.device)
     rem = _out_tensor(rem, (max(k, 0), 4), a.device)
-    _lib.check(_lib.load().plk_poly_division_dev(field, ctypes.c_void_p(a.data_ptr()), la, bs.ctypes.data_as(ctypes.c_void_p), bs.shape[0],
-                                                 ctypes.c_void_p(out.data_ptr()), q_len, ctypes.c_void_p(rem.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_poly_division_dev(field, _dp(a), la, _hp(bs), bs.shape[0], _dp(out), q_len, _dp(rem), _stream()))
     return out, rem
 
 
 # ---- the series inverse and the division by a divisor of any degree (polydiv_newton.hip): everything stays on the device ----
 def _status_ptr(status):
-    if status is None:
-        return None
-    assert status.is_cuda and status.dtype == torch.int32 and status.numel() >= 1 and status.is_contiguous()
-    return ctypes.c_void_p(status.data_ptr())
+    """the divisions' own status rule: None, or an int32 tensor of at least one word"""
+    if status is not None:
+        _check(status, torch.int32)
+        assert status.numel() >= 1
+    return _dp(status)
 
 
 def polynomial_inv_mod_xn_dev(field, h, n, out=None, status=None):
     """plk_poly_inv_mod_xn_dev: h (lh, 4) int64 CUDA tensor -> g (n, 4) with g h = 1 mod X^n.  status (optional): an int32 CUDA tensor of
     one word; bit 0 is OR-ed in when h[0] == 0 (g is unspecified then).  Nothing is synchronised."""
-    assert h.is_cuda and h.dtype == torch.int64 and h.is_contiguous() and h.dim() == 2 and h.shape[1] == 4
+    _check(h, shape=(None, 4))
     out = _out_tensor(out, (n, 4), h.device)
-    _lib.check(_lib.load().plk_poly_inv_mod_xn_dev(n, field, ctypes.c_void_p(h.data_ptr()), h.shape[0], ctypes.c_void_p(out.data_ptr()), _status_ptr(status),
-                                                   _stream()))
+    _lib.check(_lib.load().plk_poly_inv_mod_xn_dev(n, field, _dp(h), h.shape[0], _dp(out), _status_ptr(status), _stream()))
     return out
 
 
@@ -465,14 +420,13 @@ def polynomial_div_rem_dev(field, a, b, q_len=None, out=None, rem=None, status=N
     the quotient followed by zeros (q_len defaults to la - k), rem (k, 4).  status (optional): an int32 CUDA tensor of one word; bit 1 is
     OR-ed in when b[k] == 0 (the outputs are unspecified then).  Nothing is synchronised."""
     for t in (a, b):
-        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4
+        _check(t, shape=(None, 4))
     la, k = a.shape[0], b.shape[0] - 1
     if q_len is None:
         q_len = out.shape[0] if out is not None else max(la - k, 0)
     out = _out_tensor(out, (q_len, 4), a.device)
     rem = _out_tensor(rem, (max(k, 0), 4), a.device)
-    _lib.check(_lib.load().plk_poly_div_rem_dev(la, field, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), b.shape[0],
-                                                ctypes.c_void_p(out.data_ptr()), q_len, ctypes.c_void_p(rem.data_ptr()), _status_ptr(status), _stream()))
+    _lib.check(_lib.load().plk_poly_div_rem_dev(la, field, _dp(a), _dp(b), b.shape[0], _dp(out), q_len, _dp(rem), _status_ptr(status), _stream()))
     return out, rem
 
 
@@ -481,62 +435,55 @@ def public_input_quotient_dev(field, wire_polys_no_pis, alpha, roots, degree):
     by prod (X - roots[i]) over the public-input rows -> (quotient padded to `degree`, remainder (k, 4): zero for a valid witness).
     api.powers (the nine powers of alpha, host scalars: a call on the library's own lane) + reduce_polynomials_dev + plk_poly_from_roots + the
     division; the polynomials stay on the device and the caller's stream is never synchronised."""
-    from .api import polynomial_from_roots, powers
-    pw = powers(field, alpha, len(wire_polys_no_pis))  # host scalars of the reduction: the caller's stream is not touched
+    pw = _api.powers(field, alpha, len(wire_polys_no_pis))  # host scalars of the reduction: the caller's stream is not touched
     scaled = reduce_polynomials_dev(field, [p[:degree] for p in wire_polys_no_pis], pw, degree)
-    return polynomial_division_dev(field, scaled, polynomial_from_roots(field, roots), q_len=degree)
+    return polynomial_division_dev(field, scaled, _api.polynomial_from_roots(field, roots), q_len=degree)
 
 
 # ---- one round of the inner-product argument (halo.rs:63-124) on device-resident vectors ----
-def _limbs(x, n=4):
-    return np.ascontiguousarray(x, dtype=np.uint64).reshape(n)
-
-
 def inner_product_dev(field, a, b):
     """Field::inner_product (field.rs:213-221) -> (1, 4) int64 CUDA tensor."""
-    assert a.is_cuda and b.is_cuda and a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+    _check(a, None)
+    _check(b, None, shape=a.shape)
     out = torch.empty((1, a.shape[-1]), dtype=torch.int64, device=a.device)
-    _lib.check(_lib.load().plk_field_inner_product_dev(field, ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), a.shape[0],
-                                                       ctypes.c_void_p(out.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_field_inner_product_dev(field, _dp(a), _dp(b), a.shape[0], _dp(out), _stream()))
     return out
 
 
 def fold_slices_dev(field, lo, hi, scalar_lo, scalar_hi):
     """scalar_lo * lo + scalar_hi * hi (add_slices of scale_slice, halo.rs:117-118)."""
-    assert lo.is_cuda and hi.is_cuda and lo.is_contiguous() and hi.is_contiguous() and lo.shape == hi.shape
+    _check(lo, None)
+    _check(hi, None, shape=lo.shape)
     out = torch.empty_like(lo)
-    sl, sh = _limbs(scalar_lo, lo.shape[-1]), _limbs(scalar_hi, lo.shape[-1])
-    _lib.check(_lib.load().plk_field_fold_slices_dev(field, ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(hi.data_ptr()),
-                                                     sl.ctypes.data_as(ctypes.c_void_p), sh.ctypes.data_as(ctypes.c_void_p), lo.shape[0],
-                                                     ctypes.c_void_p(out.data_ptr()), _stream()))
+    sl, sh = _u64(scalar_lo, lo.shape[-1]), _u64(scalar_hi, lo.shape[-1])
+    _lib.check(_lib.load().plk_field_fold_slices_dev(field, _dp(lo), _dp(hi), _hp(sl), _hp(sh), lo.shape[0], _dp(out), _stream()))
     return out
 
 
 def fold_generators_dev(curve, g_lo, g_hi, scalar_lo, scalar_hi, lo_zero=None, hi_zero=None):
     """G' = [scalar_lo] G_lo + [scalar_hi] G_hi pair by pair (halo.rs:119-123) -> ((m, 2, L), (m,) zero flags) on device."""
-    assert g_lo.is_cuda and g_hi.is_cuda and g_lo.is_contiguous() and g_hi.is_contiguous() and g_lo.shape == g_hi.shape
+    _check(g_lo, None)
+    _check(g_hi, None, shape=g_lo.shape)
     m = g_lo.shape[0]
     out = torch.empty_like(g_lo)
     oz = torch.empty((m,), dtype=torch.uint8, device=g_lo.device)
-    sl, sh = _limbs(scalar_lo), _limbs(scalar_hi)
-    zp = lambda z: ctypes.c_void_p(z.data_ptr()) if z is not None else None
-    _lib.check(_lib.load().plk_curve_fold_pairs_dev(curve, m, ctypes.c_void_p(g_lo.data_ptr()), zp(lo_zero), ctypes.c_void_p(g_hi.data_ptr()), zp(hi_zero),
-                                                    sl.ctypes.data_as(ctypes.c_void_p), sh.ctypes.data_as(ctypes.c_void_p),
-                                                    ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(oz.data_ptr()), _stream()))
+    sl, sh = _u64(scalar_lo, 4), _u64(scalar_hi, 4)
+    _lib.check(_lib.load().plk_curve_fold_pairs_dev(curve, m, _dp(g_lo), _dp(lo_zero), _dp(g_hi), _dp(hi_zero), _hp(sl), _hp(sh), _dp(out), _dp(oz),
+                                                    _stream()))
     return out, oz
 
 
 def fold_generators_multi_dev(curve, g, scalars, log_inputs, g_zero=None):
     """out_i = g_i + sum_{t >= 1} [s_t] g_{i + t n_out}, n_out = len(g) >> log_inputs (plk_curve_fold_multi_dev): g (n, 2, L) CUDA,
     scalars (2^log_inputs, 4) CUDA int64 (Montgomery, scalar field) with the scalar of input t at index bitreverse(t)."""
-    assert g.is_cuda and g.is_contiguous() and scalars.is_cuda and scalars.is_contiguous() and scalars.shape[0] == 1 << log_inputs
+    _check(g, None)
+    _check(scalars, None)
+    assert scalars.shape[0] == 1 << log_inputs
     n_out = g.shape[0] >> log_inputs
     assert n_out << log_inputs == g.shape[0]
     out = torch.empty((n_out,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
     oz = torch.empty((n_out,), dtype=torch.uint8, device=g.device)
-    _lib.check(_lib.load().plk_curve_fold_multi_dev(curve, n_out, log_inputs, ctypes.c_void_p(g.data_ptr()),
-                                                    ctypes.c_void_p(g_zero.data_ptr()) if g_zero is not None else None,
-                                                    ctypes.c_void_p(scalars.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(oz.data_ptr()), _stream()))
+    _lib.check(_lib.load().plk_curve_fold_multi_dev(curve, n_out, log_inputs, _dp(g), _dp(g_zero), _dp(scalars), _dp(out), _dp(oz), _stream()))
     return out, oz
 
 
@@ -545,12 +492,11 @@ def halo_round_lr_dev(curve, halo_a, halo_b, halo_g, pedersen_h, u_prime, l_blin
     halo_a / halo_b: (n, 4) scalars, halo_g: (n, 2, L) affine generators (g_zero: (n,) identity flags or None); pedersen_h /
     u_prime: (2, L) affine host points; the blinding factors are host scalars.  The msm_parallel, the blinding term and the
     inner-product term are ONE table-free MSM over [G_half..., H, U'] each.  Returns ((2, 2, L), (2,)): L_j then R_j, affine."""
-    from .api import CURVE_SCALAR_FIELD
     n = halo_a.shape[0]
     m = n // 2
-    sf = CURVE_SCALAR_FIELD[curve]
+    sf = _api.CURVE_SCALAR_FIELD[curve]
     L = _CURVE_LIMBS[curve]
-    extra = to_device(np.stack([np.ascontiguousarray(pedersen_h, dtype=np.uint64).reshape(2, L), np.ascontiguousarray(u_prime, dtype=np.uint64).reshape(2, L)]))
+    extra = to_device(np.stack([_u64(pedersen_h, 2, L), _u64(u_prime, 2, L)]))
     # L_j and R_j are independent and, below 2^16 points, pure latency (the window-doubling chain of a table-free MSM):
     # they run on two streams
     main = torch.cuda.current_stream()
@@ -562,7 +508,7 @@ def halo_round_lr_dev(curve, halo_a, halo_b, halo_g, pedersen_h, u_prime, l_blin
         st = main if k == 0 else side
         with torch.cuda.stream(st):
             ip = inner_product_dev(sf, a_half.contiguous(), b_half.contiguous())
-            scal = torch.cat([a_half, to_device(_limbs(blind).reshape(1, 4)), ip], dim=0).contiguous()
+            scal = torch.cat([a_half, to_device(_u64(blind, 1, 4)), ip], dim=0).contiguous()
             bases = torch.cat([g_half, extra], dim=0).contiguous()
             zf = None
             if gz is not None:
@@ -594,9 +540,8 @@ def _side_stream(device):
 
 def halo_round_fold_dev(curve, halo_a, halo_b, halo_g, u_j, u_j_inv, g_zero=None):
     """halo_a' = u^-1 a_hi + u a_lo, halo_b' = u^-1 b_lo + u b_hi, G' = [u^-1] G_lo + [u] G_hi (halo.rs:117-123)."""
-    from .api import CURVE_SCALAR_FIELD
     m = halo_a.shape[0] // 2
-    sf = CURVE_SCALAR_FIELD[curve]
+    sf = _api.CURVE_SCALAR_FIELD[curve]
     a2 = fold_slices_dev(sf, halo_a[m:].contiguous(), halo_a[:m].contiguous(), u_j_inv, u_j)
     b2 = fold_slices_dev(sf, halo_b[:m].contiguous(), halo_b[m:].contiguous(), u_j_inv, u_j)
     g2, gz2 = fold_generators_dev(curve, halo_g[:m].contiguous(), halo_g[m:].contiguous(), u_j_inv, u_j,
@@ -613,30 +558,24 @@ class HaloArgument:
     def __init__(self, curve, halo_a, halo_b, halo_g, pedersen_h, u_prime, g_zero=None, freeze_log=0, tables=None, lead_rounds=0, h_index=None, u_index=None,
                  u_prime_scalar=None):
         for t in (halo_a, halo_b, halo_g):
-            assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+            _check(t)
         n = halo_a.shape[0]
         assert halo_b.shape[0] == n and halo_g.shape[0] == n
         self.curve, self.L = curve, _CURVE_LIMBS[curve]
-        h = np.ascontiguousarray(pedersen_h, dtype=np.uint64).reshape(2, self.L)
-        u = np.ascontiguousarray(u_prime, dtype=np.uint64).reshape(2, self.L)
+        h, u = _u64(pedersen_h, 2, self.L), _u64(u_prime, 2, self.L)
         ctx = ctypes.c_void_p()
-        zp = ctypes.c_void_p(g_zero.data_ptr()) if g_zero is not None else None
+        vectors = (curve, n, _dp(halo_a), _dp(halo_b), _dp(halo_g), _dp(g_zero))
         if tables is not None:
             # tables: the MsmPrecomputation (msm_precompute_dev) of pedersen_g the caller commits with - the first rounds run over it
             # h_index / u_index / u_prime_scalar: pedersen_h and the fixed generator U inside those tables, u_prime = [u_prime_scalar] U
             self._tables = tables  # must outlive the lead rounds
             NO = ctypes.c_size_t(-1).value
             inside = u_prime_scalar is not None and h_index is not None and u_index is not None
-            xs = _limbs(u_prime_scalar) if inside else None
-            _lib.check(_lib.load().plk_halo_begin_tabled_dev(curve, n, ctypes.c_void_p(halo_a.data_ptr()), ctypes.c_void_p(halo_b.data_ptr()),
-                                                             ctypes.c_void_p(halo_g.data_ptr()), zp, tables._ctx, h.ctypes.data_as(ctypes.c_void_p),
-                                                             u.ctypes.data_as(ctypes.c_void_p), h_index if inside else NO, u_index if inside else NO,
-                                                             xs.ctypes.data_as(ctypes.c_void_p) if inside else None, freeze_log, lead_rounds, _stream(),
-                                                             ctypes.byref(ctx)))
+            xs = _u64(u_prime_scalar, 4) if inside else None
+            _lib.check(_lib.load().plk_halo_begin_tabled_dev(*vectors, tables._ctx, _hp(h), _hp(u), h_index if inside else NO, u_index if inside else NO,
+                                                             _hp(xs) if inside else None, freeze_log, lead_rounds, _stream(), ctypes.byref(ctx)))
         else:
-            _lib.check(_lib.load().plk_halo_begin_dev(curve, n, ctypes.c_void_p(halo_a.data_ptr()), ctypes.c_void_p(halo_b.data_ptr()),
-                                                      ctypes.c_void_p(halo_g.data_ptr()), zp, h.ctypes.data_as(ctypes.c_void_p),
-                                                      u.ctypes.data_as(ctypes.c_void_p), freeze_log, _stream(), ctypes.byref(ctx)))
+            _lib.check(_lib.load().plk_halo_begin_dev(*vectors, _hp(h), _hp(u), freeze_log, _stream(), ctypes.byref(ctx)))
         self._ctx = ctx
 
     def __len__(self):
@@ -650,25 +589,23 @@ class HaloArgument:
         """(L_j, R_j) as a (2, 2, L) uint64 array + (2,) identity flags, on the host (the transcript's input)."""
         lr = np.empty((2, 2, self.L), dtype=np.uint64)
         z = np.zeros(2, dtype=np.uint8)
-        lb, rb = _limbs(l_blinding), _limbs(r_blinding)
-        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(_lib.load().plk_halo_round_lr(self._ctx, p(lb), p(rb), p(lr), p(z)))
+        lb, rb = _u64(l_blinding, 4), _u64(r_blinding, 4)
+        _lib.check(_lib.load().plk_halo_round_lr(self._ctx, _hp(lb), _hp(rb), _hp(lr), _hp(z)))
         return lr, z
 
     def round_fold(self, u_j, u_j_inv):
-        u, ui = _limbs(u_j), _limbs(u_j_inv)
-        _lib.check(_lib.load().plk_halo_round_fold(self._ctx, u.ctypes.data_as(ctypes.c_void_p), ui.ctypes.data_as(ctypes.c_void_p)))
+        u, ui = _u64(u_j, 4), _u64(u_j_inv, 4)
+        _lib.check(_lib.load().plk_halo_round_fold(self._ctx, _hp(u), _hp(ui)))
 
     def read(self, with_g=True):
         """(halo_a, halo_b[, halo_g, g_zero]) on the host; halo_g of frozen generators exists at length 1 only."""
         n = len(self)
         a, b = np.empty((n, 4), dtype=np.uint64), np.empty((n, 4), dtype=np.uint64)
-        p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
         if not with_g:
-            _lib.check(_lib.load().plk_halo_read(self._ctx, p(a), p(b), None, None))
+            _lib.check(_lib.load().plk_halo_read(self._ctx, _hp(a), _hp(b), None, None))
             return a, b
         g, gz = np.empty((n, 2, self.L), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
-        _lib.check(_lib.load().plk_halo_read(self._ctx, p(a), p(b), p(g), p(gz)))
+        _lib.check(_lib.load().plk_halo_read(self._ctx, _hp(a), _hp(b), _hp(g), _hp(gz)))
         return a, b, g, gz
 
     def free(self):
@@ -686,25 +623,19 @@ class HaloArgument:
 # ---- Rescue on device-resident tensors (rescue.rs, field.rs:340-375); ctx: api.RescueContext ----
 def rescue_permutation_dev(ctx, states, out=None):
     """rescue_permutation per state: states (n, 4, L) int64 CUDA tensor, Montgomery form; out may be states itself (in place)."""
-    L = _FIELD_LIMBS[ctx.field]
-    assert states.is_cuda and states.dtype == torch.int64 and states.is_contiguous() and states.shape[1:] == (ctx.width, L)
-    if out is None:
-        out = torch.empty_like(states)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == states.shape
-    _lib.check(_lib.load().plk_rescue_permutation_dev(states.shape[0], ctx.handle, ctypes.c_void_p(states.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+    _check(states, shape=(None, ctx.width, _FIELD_LIMBS[ctx.field]))
+    out = _out_tensor(out, states.shape, states.device)
+    _lib.check(_lib.load().plk_rescue_permutation_dev(states.shape[0], ctx.handle, _dp(states), _dp(out), _stream()))
     return out
 
 
 def rescue_sponge_dev(ctx, inputs, num_outputs, out=None):
     """rescue_sponge per row: inputs (n, n_inputs, L) int64 CUDA tensor (n_inputs may be 0) -> (n, num_outputs, L).  One launch."""
     L = _FIELD_LIMBS[ctx.field]
-    assert inputs.is_cuda and inputs.dtype == torch.int64 and inputs.is_contiguous() and inputs.dim() == 3 and inputs.shape[2] == L
+    _check(inputs, shape=(None, None, L))
     n, n_inputs = inputs.shape[0], inputs.shape[1]
-    if out is None:
-        out = torch.empty((n, num_outputs, L), dtype=torch.int64, device=inputs.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (n, num_outputs, L)
-    _lib.check(_lib.load().plk_rescue_sponge_dev(n, ctx.handle, n_inputs, ctypes.c_void_p(inputs.data_ptr()), num_outputs, ctypes.c_void_p(out.data_ptr()),
-                                                 _stream()))
+    out = _out_tensor(out, (n, num_outputs, L), inputs.device)
+    _lib.check(_lib.load().plk_rescue_sponge_dev(n, ctx.handle, n_inputs, _dp(inputs), num_outputs, _dp(out), _stream()))
     return out
 
 
@@ -718,53 +649,42 @@ def rescue_hash_to_curve_dev(ctx, curve, count, seed_start=0, out=None, device="
     """hash_usize_to_curve (hash_to_curve.rs:8-11, 78-104) of the integers seed_start .. seed_start + count - 1 on the device; ctx: an
     api.RescueContext over the curve's base field, its rounds standing for security_bits.  (count, 2, L) int64 tensor that
     msm_precompute_dev takes as it is."""
-    L = _CURVE_LIMBS[curve]
-    if out is None:
-        out = torch.empty((count, 2, L), dtype=torch.int64, device=device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
-    _rescue_h2c_call(_lib.load().plk_rescue_hash_to_curve_dev(count, ctx.handle, curve, int(seed_start), ctypes.c_void_p(out.data_ptr()), _stream()))
+    out = _out_tensor(out, (count, 2, _CURVE_LIMBS[curve]), device)
+    assert out.is_cuda  # a fresh one too: `device` is the caller's word
+    _rescue_h2c_call(_lib.load().plk_rescue_hash_to_curve_dev(count, ctx.handle, curve, int(seed_start), _dp(out), _stream()))
     return out
 
 
 def rescue_hash_field_to_curve_dev(ctx, curve, seeds, out=None):
     """hash_base_field_to_curve per row: seeds (count, L) int64 CUDA tensor, Montgomery form -> (count, 2, L)."""
     L = _CURVE_LIMBS[curve]
-    assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.dim() == 2 and seeds.shape[1] == L
+    _check(seeds, shape=(None, L))
     count = seeds.shape[0]
-    if out is None:
-        out = torch.empty((count, 2, L), dtype=torch.int64, device=seeds.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == (count, 2, L)
-    _rescue_h2c_call(_lib.load().plk_rescue_hash_field_to_curve_dev(count, ctx.handle, curve, ctypes.c_void_p(seeds.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                                  _stream()))
+    out = _out_tensor(out, (count, 2, L), seeds.device)
+    _rescue_h2c_call(_lib.load().plk_rescue_hash_field_to_curve_dev(count, ctx.handle, curve, _dp(seeds), _dp(out), _stream()))
     return out
 
 
 def kth_root_dev(field, x, k, out=None):
     """Field::kth_root_u32(k) per element: x (n, L) int64 CUDA tensor; out may be x itself."""
-    assert x.is_cuda and x.dtype == torch.int64 and x.is_contiguous() and x.shape[-1] == _FIELD_LIMBS[field]
-    if out is None:
-        out = torch.empty_like(x)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == x.shape
-    _lib.check(_lib.load().plk_field_kth_root_dev(x.numel() // x.shape[-1], field, int(k), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), _stream()))
+    _check(x, last=(_FIELD_LIMBS[field],))
+    out = _out_tensor(out, x.shape, x.device)
+    _lib.check(_lib.load().plk_field_kth_root_dev(x.numel() // x.shape[-1], field, int(k), _dp(x), _dp(out), _stream()))
     return out
 
 
 # ---- a point times a scalar of its own and the Halo endomorphism on device-resident tensors (scalar_mul.hip) ----
 def _scalar_mul_tensors(curve, scalars, points, zero, out, out_zero):
     L = _CURVE_LIMBS[curve]
-    ok = lambda t: t.is_cuda and t.is_contiguous()
-    assert ok(scalars) and scalars.dtype == torch.int64 and scalars.shape[-1] == 4
-    assert ok(points) and points.dtype == torch.int64 and points.shape[-2:] == (2, L)
+    _check(scalars, last=(4,))
+    _check(points, last=(2, L))
     ns, npts = scalars.numel() // 4, points.numel() // (2 * L)
     count = max(ns, npts)
-    assert zero is None or (ok(zero) and zero.dtype == torch.uint8 and zero.numel() == npts)
-    if out is None:
-        out = torch.empty((count, 2, L), dtype=torch.int64, device=points.device)
-    if out_zero is None:
-        out_zero = torch.empty(count, dtype=torch.uint8, device=points.device)
-    assert ok(out) and out.dtype == torch.int64 and out.numel() == count * 2 * L and ok(out_zero) and out_zero.dtype == torch.uint8 and out_zero.numel() == count
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    return count, ns, npts, p(scalars), p(points), p(zero), p(out), p(out_zero), out, out_zero
+    if zero is not None:
+        _check(zero, torch.uint8, numel=npts)
+    out = _out_tensor(out, (count, 2, L), points.device, check="numel")
+    out_zero = _out_tensor(out_zero, (count,), points.device, torch.uint8, check="numel")
+    return count, ns, npts, _dp(scalars), _dp(points), _dp(zero), _dp(out), _dp(out_zero), out, out_zero
 
 
 def scalar_mul_dev(curve, scalars, points, zero=None, out=None, out_zero=None):
@@ -777,12 +697,9 @@ def scalar_mul_dev(curve, scalars, points, zero=None, out=None, out_zero=None):
 
 def halo_n_dev(curve, scalars, security_bits=128, out=None):
     """n(s_i) of the low security_bits bits: scalars (n, 4) int64 CUDA tensor; out may be scalars itself."""
-    assert scalars.is_cuda and scalars.dtype == torch.int64 and scalars.is_contiguous() and scalars.shape[-1] == 4
-    if out is None:
-        out = torch.empty_like(scalars)
-    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.shape == scalars.shape
-    _lib.check(_lib.load().plk_halo_n_dev(scalars.numel() // 4, curve, int(security_bits), ctypes.c_void_p(scalars.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                          _stream()))
+    _check(scalars, last=(4,))
+    out = _out_tensor(out, scalars.shape, scalars.device)
+    _lib.check(_lib.load().plk_halo_n_dev(scalars.numel() // 4, curve, int(security_bits), _dp(scalars), _dp(out), _stream()))
     return out
 
 

@@ -2,8 +2,6 @@
 rank, ONE all-gather of the packed partial results, point sum on the device.  Independent NTTs need no
 collective.  Backend-agnostic: nccl (= RCCL over xGMI) on the GPUs; gloo in the CPU tests and when several
 ranks share one GPU (the payload - a few hundred bytes - is then staged through host memory)."""
-import ctypes
-
 import torch
 import torch.distributed as dist
 
@@ -144,10 +142,10 @@ class PartialExchange:
     def combine(self):
         """The `batch` results in vector order -> (sum_xy (batch, 2, L), sum_zero (batch,)) on the device."""
         from . import lib as _lib
+        from .device import _dp, _stream
         assert self.recv.is_cuda, "the point sum runs on the GPU (there is no CPU path)"
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(_lib.load().plk_msm_combine_partials_dev(self.curve, self.world, self.batch, self.whole, ctypes.c_void_p(self.recv.data_ptr()),
-                                                            ctypes.c_void_p(self.sum_xy.data_ptr()), ctypes.c_void_p(self.sum_zero.data_ptr()), st))
+        _lib.check(_lib.load().plk_msm_combine_partials_dev(self.curve, self.world, self.batch, self.whole, _dp(self.recv), _dp(self.sum_xy),
+                                                            _dp(self.sum_zero), _stream()))
         return self.sum_xy, self.sum_zero
 
     def partials(self):
