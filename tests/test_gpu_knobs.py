@@ -20,9 +20,9 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-NTT = ["tests/test_gpu_parity.py", "tests/test_gpu_poly.py", "-k",
+NTT = ["tests/test_gpu_parity.py", "tests/test_gpu_poly.py", "tests/test_gpu_ntt_structured.py", "-k",
        "test_fft_and_ifft or (test_ntt_matches_oracle and (Tweedledee or Bls12377Base)) or test_ntt_linearity or test_ntt_padding or "
-       "test_polynomials_to_values_padded or test_division_by_z_h_plonk_shape or test_ntt_2p20_full_size"]
+       "test_polynomials_to_values_padded or test_division_by_z_h_plonk_shape or test_ntt_2p20_full_size or test_structured_ntt_default_plan or test_padded_lengths_match_oracle"]
 MSM = ["tests/test_gpu_parity.py", "-k",
        "test_msm_tweedledee_mini_kat or (test_msm_matches_oracle and (Tweedledee or Bls12377)) or test_msm_parallel_one_shot or "
        "test_msm_batch_and_sum_affine or test_msm_batch_larger_than_one_group or test_coeffs_vec_to_commitments or test_msm_heavy_buckets"]
