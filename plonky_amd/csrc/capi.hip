@@ -1,288 +1,12 @@
 // capi.hip -- the extern "C" surface declared in include/plonky_hip.h.
-// Thin: argument validation, host<->device staging for the host-pointer variants, dispatch.
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <cstdarg>
+// Thin: argument validation, host<->device staging for the host-pointer variants (LaneCall, host_lane.h), dispatch.  Only the
+// entry points and their file-local helpers live here: the state they lean on is host_runtime.hip's.
 #include <cstring>
-#include <map>
 #include <memory>
 #include <new>
-#include <mutex>
-#include <thread>
 #include <vector>
 
-#include "common.h"
-#include "ec.cuh"
 #include "host_lane.h"
-#include "pin_registry.h"
-
-struct plk_msm_ctx;
-struct plk_halo_ctx;
-
-namespace plk {
-
-int halo_begin_dev_impl(int curve, size_t n, const void* d_a, const void* d_b, const void* d_g, const void* d_gz, const uint64_t* h_xy,
-                        const uint64_t* u_xy, unsigned freeze_log, hipStream_t stream, plk_halo_ctx** out, plk_msm_ctx* tables = nullptr,
-                        unsigned lead_rounds = 0, size_t h_index = (size_t)-1, size_t u_index = (size_t)-1, const uint64_t* u_prime_scalar = nullptr);
-int curve_fold_multi_dev_impl(int curve, size_t n_out, int r_bits, const void* d_g, const void* d_gz, const void* d_ratios, void* d_out_xy,
-                              void* d_out_zero, hipStream_t stream);
-int halo_round_lr_impl(plk_halo_ctx* c, const uint64_t* l_blind, const uint64_t* r_blind, uint64_t* lr_xy, uint8_t* lr_zero);
-int halo_round_fold_impl(plk_halo_ctx* c, const uint64_t* u_j, const uint64_t* u_j_inv);
-size_t halo_len_impl(const plk_halo_ctx* c);
-int halo_frozen_impl(const plk_halo_ctx* c);
-int halo_read_impl(plk_halo_ctx* c, uint64_t* a, uint64_t* b, uint64_t* g_xy, uint8_t* g_zero);
-void halo_delete(plk_halo_ctx* c);
-
-int field_op_impl(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
-int msm_precompute_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned window_bits, unsigned flags, hipStream_t stream,
-                            plk_msm_ctx** out_ctx, const void* d_extra = nullptr, size_t n_extra = 0, const size_t* also_n = nullptr,
-                            int also_count = 0);
-int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars, size_t n_scalars, void* d_out_xy, void* d_out_zero, hipStream_t stream,
-                         hipEvent_t* ready = nullptr, const MsmParts* parts = nullptr, unsigned out_flags = 0);
-int msm_reserve_workspaces_impl(plk_msm_ctx* ctx, unsigned count, hipStream_t stream);
-int curve_sum_affine_dev_impl(int curve, size_t k, const void* d_pts, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
-int curve_gen_bases_dev_impl(int curve, size_t n, uint64_t first, const void* d_g0d, void* d_out, hipStream_t stream);
-size_t msm_partials_bytes(int curve, unsigned batch);
-int checked_build_impl();
-int checked_failures_impl(unsigned* counts);
-int msm_debug_digits_impl(int curve, unsigned window_bits, size_t n, const void* d_scalars, void* d_digits, hipStream_t stream);
-int msm_debug_digit_count(int curve, unsigned window_bits);
-int bench_ceilings_impl(double* out, unsigned n_out);
-int msm_combine_partials_dev_impl(int curve, unsigned world, unsigned batch, unsigned whole_per_rank, const void* d_gathered, void* d_out_xy, void* d_out_zero,
-                                  hipStream_t stream);
-int curve_fold_pairs_dev_impl(int curve, size_t m, const void* d_lo, const void* d_lo_zero, const void* d_hi, const void* d_hi_zero,
-                              const uint64_t* a_mont, const uint64_t* b_mont, void* d_out_xy, void* d_out_zero, hipStream_t stream,
-                              const void* d_scalars = nullptr, int plus_lo = 0);
-int msm_table_digits(int curve, unsigned w);
-int msm_reference_table_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned w, void* d_out_xy, void* d_out_zero,
-                                 hipStream_t stream);
-int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t quads, uint32_t* counts);
-int curve_op_dev_impl(int curve, int op, unsigned param, uint32_t count, const void* d_a_xy, const void* d_a_zero, const void* d_a_lambda, const void* d_b_xy,
-                      const void* d_b_zero, const void* d_b_lambda, const void* d_flags, void* d_out_xy, void* d_out_zero, void* d_mismatch);
-int msm_set_profiling_impl(plk_msm_ctx* ctx, int enable);
-int msm_get_timings_impl(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
-int ntt_set_profiling_impl(int enable);
-int ntt_get_timings_impl(double* sum_ms, unsigned* launches);
-int poly_divide_by_z_h_dev_impl(int field, const void* d_coeffs, size_t len, size_t n, void* d_out, size_t out_cap, size_t* out_len,
-                                hipStream_t stream);
-int poly_mul_dev_impl(int field, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t out_cap, size_t* out_len,
-                      hipStream_t stream);
-int ntt_padded_dev_impl(int field, unsigned log_n, unsigned batch, const void* d_in, size_t in_len, size_t in_stride, void* d_out,
-                        hipStream_t stream);
-size_t msm_ctx_len(const plk_msm_ctx* ctx);
-unsigned msm_ctx_window(const plk_msm_ctx* ctx);
-int msm_ctx_curve(const plk_msm_ctx* ctx);
-int msm_ctx_is_comb(const plk_msm_ctx* ctx);
-int msm_affine_to_projective_impl(int curve, unsigned batch, const void* d_xy, const void* d_zero, void* d_xyz, hipStream_t stream);
-void msm_ctx_delete(plk_msm_ctx* ctx);
-// multi.hip
-void multi_plan_slot(int world, unsigned batch, size_t n, int d, unsigned slot, unsigned* vec, size_t* first, size_t* count);
-bool msm_ctx_is_multi(plk_msm_ctx* ctx);
-void group_copy_stats(unsigned long long* peer, unsigned long long* staged);
-int msm_ctx_device(const plk_msm_ctx* ctx);
-int msm_precompute_multi(int curve, size_t n, const void* bases, const void* zero, bool host_src, unsigned window_bits, hipStream_t caller_stream,
-                         plk_msm_ctx** out_ctx);
-int msm_execute_multi(plk_msm_ctx* ctx, unsigned batch, const void* const* vecs, bool host_src, size_t n, void* d_out_xy, void* d_out_zero,
-                      hipStream_t caller_stream);
-
-std::string& last_error_ref() {
-    static thread_local std::string s;
-    return s;
-}
-int set_error(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    last_error_ref() = buf;
-    return code;
-}
-
-// ---- scratch pool ----
-struct ScratchEntry {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;
-    bool in_call = false;   // between acquire and release on some host thread
-    bool used = false;      // ev has been recorded at least once
-};
-static std::mutex g_scratch_mu;
-static std::vector<ScratchEntry> g_scratch;
-
-void* scratch_acquire(size_t bytes, hipStream_t stream) {
-    if (bytes == 0) bytes = 16;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    ScratchEntry* best = nullptr;
-    for (auto& e : g_scratch) {
-        if (e.in_call || e.device != dev || e.bytes < bytes) continue;
-        // a small request must not take (and keep) a buffer sized for a whole transform: at most 4x the request above 1 MiB
-        if (e.bytes > ((size_t)1 << 20) && e.bytes / 4 > bytes) continue;
-        const bool ordered = !e.used || e.stream == stream || hipEventQuery(e.ev) == hipSuccess;
-        if (!ordered) continue;
-        if (!best || e.bytes < best->bytes) best = &e;
-    }
-    if (best) {
-        best->in_call = true;
-        return best->p;
-    }
-    ScratchEntry e;
-    e.bytes = bytes;
-    e.device = dev;
-    hipError_t err = hipMalloc(&e.p, bytes);
-    if (err != hipSuccess) {
-        set_error(err == hipErrorOutOfMemory ? PLK_ERR_OOM : PLK_ERR_HIP, "hipMalloc(%zu) for scratch failed: %s", bytes, hipGetErrorString(err));
-        return nullptr;
-    }
-    if (hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipFree(e.p);
-        set_error(PLK_ERR_HIP, "hipEventCreate failed");
-        return nullptr;
-    }
-    e.in_call = true;
-    g_scratch.push_back(e);
-    return e.p;
-}
-
-void scratch_release(void* p, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    for (auto& e : g_scratch)
-        if (e.p == p) {
-            (void)hipEventRecord(e.ev, stream);
-            e.stream = stream;
-            e.used = true;
-            e.in_call = false;
-            return;
-        }
-}
-
-struct PooledStream {
-    hipStream_t s;
-    int device;
-    bool free;
-};
-static std::mutex g_spool_mu;
-static std::vector<PooledStream> g_spool;
-
-hipStream_t stream_pool_acquire() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g_spool_mu);
-    for (auto& e : g_spool)
-        if (e.free && e.device == dev) {
-            e.free = false;
-            return e.s;
-        }
-    hipStream_t s = nullptr;
-    hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (err != hipSuccess) {
-        set_error(PLK_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(err));
-        return nullptr;
-    }
-    g_spool.push_back({s, dev, false});
-    return s;
-}
-void stream_pool_release(hipStream_t s) {
-    if (!s) return;
-    std::lock_guard<std::mutex> lk(g_spool_mu);
-    for (auto& e : g_spool)
-        if (e.s == s) e.free = true;
-}
-
-void scratch_clear() {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (int d = 0; d < group_size(); ++d) {  // every device of the group is quiet before its buffers go
-        if (d && group_phys(d) == group_phys(d - 1)) continue;
-        (void)hipSetDevice(group_phys(d));
-        (void)hipDeviceSynchronize();
-    }
-    (void)hipSetDevice(cur);
-    (void)hipDeviceSynchronize();
-    for (auto& e : g_scratch) {
-        if (e.in_call) continue;
-        (void)hipFree(e.p);
-        (void)hipEventDestroy(e.ev);
-        e.p = nullptr;
-    }
-    std::vector<ScratchEntry> keep;
-    for (auto& e : g_scratch)
-        if (e.p) keep.push_back(e);
-    g_scratch.swap(keep);
-}
-
-// ---- host-pointer entry points: one lane per (calling thread, logical device) - host_lane.h ----
-static thread_local HostLane t_lanes[PLK_MAX_DEVICES];
-
-int lane_get(HostLane*& out) {
-    PLK_TRY(ensure_device());
-    int dev = 0;
-    PLK_HIP_TRY(hipGetDevice(&dev));
-    HostLane& l = t_lanes[thread_logical_device()];
-    if (l.stream && l.device != dev) l.drop_streams();  // the group was re-initialised over other devices
-    if (!l.stream) {
-        l.stream = stream_pool_acquire();
-        if (!l.stream) return PLK_ERR_HIP;
-        l.device = dev;
-    }
-    if (l.pin_used) (void)hipStreamSynchronize(l.stream);  // a call that failed half way may have left copies in flight
-    l.pin_used = 0;
-    out = &l;
-    return PLK_OK;
-}
-
-// The caller-buffer registry (pin_registry.h has the rules and the code; host_lane.h the callers): here only its three outside
-// effects - hipHostRegister as portable (every device of the group may copy from the range), hipHostUnregister, and "every device
-// of the group quiet" - and the library's one instance, with the two-second wait limit.
-struct HipPinPolicy {
-    bool register_range(const uint8_t* lo, size_t bytes) {
-        if (hipHostRegister(const_cast<uint8_t*>(lo), bytes, hipHostRegisterPortable) == hipSuccess) return true;
-        (void)hipGetLastError();
-        return false;
-    }
-    void unregister_range(const uint8_t* lo) { (void)hipHostUnregister(const_cast<uint8_t*>(lo)); }
-    void quiesce() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        for (int d = 0; d < group_size(); ++d) {
-            if (d && group_phys(d) == group_phys(d - 1)) continue;
-            (void)hipSetDevice(group_phys(d));
-            (void)hipDeviceSynchronize();
-        }
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-};
-static PinRegistry<HipPinPolicy>& pin_registry() {
-    static PinRegistry<HipPinPolicy>* r = new PinRegistry<HipPinPolicy>(2000);  // never destroyed: thread-local lanes may outlive statics
-    return *r;
-}
-bool pin_registry_acquire(const void* ptr, size_t bytes) { return pin_registry().acquire(ptr, bytes); }
-void pin_registry_release(const void* ptr) { pin_registry().release(ptr); }
-
-static std::atomic<unsigned long long> g_lane_copies[LANE_ROUTES];
-void lane_count(int route) { g_lane_copies[route].fetch_add(1, std::memory_order_relaxed); }
-
-static int or_invalid_id(int rc) { return rc == PLK_NO_MATCH ? PLK_ERR_INVALID_ARG : rc; }
-int field_limbs(int field) {
-    return or_invalid_id(with_field(field, [](auto t) { return tag_t<decltype(t)>::NL / 2; }));
-}
-int curve_limbs(int curve) {
-    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::FP::NL / 2; }));
-}
-int curve_scalar_field(int curve) {
-    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::SP::FIELD_ID; }));
-}
-int curve_scalar_bits(int curve) {
-    return or_invalid_id(with_curve(curve, [](auto t) { return tag_t<decltype(t)>::SP::BITS; }));
-}
-
-}  // namespace plk
 
 using namespace plk;
 
@@ -331,15 +55,7 @@ void plk_shutdown(void) {
 // Not part of the ABI (include/plonky_hip.h does not declare it): the suite reads which route the host-pointer plumbing took.
 // out[0 .. PIN_BRANCHES): calls per branch of the caller-buffer registry (pin_registry.h: PinBranch), then its waits and rechecks,
 // then the copies per LaneRoute (host_lane.h).  Returns the number of values there are; writes at most n of them.
-int plk_internal_host_stats(unsigned long long* out, unsigned n) {
-    const PinStats ps = pin_registry().stats();
-    std::vector<unsigned long long> v(ps.branch, ps.branch + PIN_BRANCHES);
-    v.push_back(ps.waits);
-    v.push_back(ps.rechecks);
-    for (int r = 0; r < LANE_ROUTES; ++r) v.push_back(g_lane_copies[r].load(std::memory_order_relaxed));
-    for (unsigned i = 0; out && i < n && i < v.size(); ++i) out[i] = v[i];
-    return (int)v.size();
-}
+int plk_internal_host_stats(unsigned long long* out, unsigned n) { return host_stats(out, n); }
 
 const char* plk_last_error(void) { return last_error_ref().c_str(); }
 unsigned plk_min_gpu_log_n(void) {
@@ -374,15 +90,14 @@ int plk_ntt_precompute_table(int field, unsigned log_n, uint64_t* out) {
     if (field_limbs(field) < 0) return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
     if (log_n > 30) return set_error(PLK_ERR_TWO_ADICITY, "log_n %u too large (max 30)", log_n);
     if (!out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
-    HostLane* l = nullptr;
-    PLK_TRY(lane_get(l));
     const size_t bytes = (((size_t)2 << log_n) - 1) * (size_t)field_limbs(field) * 8;
-    LaneBuf buf;
-    PLK_TRY(buf.alloc(bytes, l->stream));
-    PLK_TRY(ntt_reference_table_dev_impl(field, log_n, buf.p, l->stream));
-    std::vector<LaneOut> outs;
-    PLK_TRY(lane_d2h(*l, outs, out, buf.p, bytes));
-    return lane_finish(*l, outs);
+    LaneCall c;
+    PLK_TRY(c.begin());
+    void* buf = nullptr;
+    PLK_TRY(c.tmp(buf, bytes));
+    PLK_TRY(ntt_reference_table_dev_impl(field, log_n, buf, c.stream()));
+    PLK_TRY(c.out(out, buf, bytes));
+    return c.finish();
 }
 
 int plk_ntt_dev(int field, unsigned log_n, int inverse, unsigned batch, const void* d_in, void* d_out, void* stream) {
@@ -390,9 +105,13 @@ int plk_ntt_dev(int field, unsigned log_n, int inverse, unsigned batch, const vo
     return ntt_dev_impl(field, log_n, inverse, batch, d_in, d_out, as_stream(stream));
 }
 
-// `batch` transforms from / to host memory on the calling thread's current device
-static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batch, const uint64_t* const* in, uint64_t* const* out) {
-    if (batch == 0) return PLK_OK;
+// `batch` transforms from / to host memory on the calling thread's current device.  Over a device group (deal_units) the thread's
+// share of a batch of `total` is every step-th transform from `first` on: transform b of the share is slot b * step from there.
+static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned total, const uint64_t* const* in, uint64_t* const* out, unsigned first,
+                           unsigned step) {
+    if (first >= total) return PLK_OK;
+    const unsigned batch = (total - first + step - 1) / step;
+    in += first, out += first;
     const size_t bytes = ((size_t)1 << log_n) * (size_t)field_limbs(field) * 8;  // 32 per element, 48 for Bls12377Base
     LaneCall c;
     PLK_TRY(c.begin());
@@ -401,9 +120,9 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
     PLK_TRY(c.tmp(buf, bytes * batch));
     if (batch == 1 || bytes < ((size_t)1 << 20)) {
         // one transform, or small ones: upload, one batched launch, download
-        for (unsigned b = 0; b < batch; ++b) PLK_TRY(lane_h2d(*l, (uint8_t*)buf + b * bytes, in[b], bytes));
+        for (unsigned b = 0; b < batch; ++b) PLK_TRY(lane_h2d(*l, (uint8_t*)buf + b * bytes, in[b * step], bytes));
         PLK_TRY(ntt_dev_impl(field, log_n, inverse, batch, buf, buf, l->stream));
-        for (unsigned b = 0; b < batch; ++b) PLK_TRY(c.out(out[b], (uint8_t*)buf + b * bytes, bytes));
+        for (unsigned b = 0; b < batch; ++b) PLK_TRY(c.out(out[b * step], (uint8_t*)buf + b * bytes, bytes));
         return c.finish();
     }
     // several large transforms (the nine wire polynomials, plonk_util.rs:169-190): PCIe is the long pole (2 x 32 MiB per 2^20
@@ -413,8 +132,8 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
     // (Until round 4 transform b ran upload -> kernels -> download on stream b mod 3: three uploads shared the link, nothing ran
     // before all three had landed 1.8 ms in, and the last three downloads had the link to themselves; PLK_NTT_HOST_PIPE=0 is that form.)
     for (unsigned b = 0; b < batch; ++b) {
-        c.pin(in[b], bytes);
-        if ((const void*)out[b] != (const void*)in[b]) c.pin(out[b], bytes);
+        c.pin(in[b * step], bytes);
+        if ((const void*)out[b * step] != (const void*)in[b * step]) c.pin(out[b * step], bytes);
     }
     PLK_TRY(lane_fork(*l));
     const char* pe = getenv("PLK_NTT_HOST_PIPE");
@@ -422,9 +141,9 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
         for (unsigned b = 0; b < batch; ++b) {
             hipStream_t st = b % 3 == 0 ? l->stream : l->aux[b % 3 - 1];
             uint8_t* d = (uint8_t*)buf + b * bytes;
-            PLK_TRY(lane_h2d(*l, d, in[b], bytes, st));
+            PLK_TRY(lane_h2d(*l, d, in[b * step], bytes, st));
             PLK_TRY(ntt_dev_impl(field, log_n, inverse, 1, d, d, st));
-            PLK_TRY(lane_d2h(*l, c.outs, out[b], d, bytes, st));
+            PLK_TRY(lane_d2h(*l, c.outs, out[b * step], d, bytes, st));
         }
     } else {
         while (l->ev_ready.size() < 2 * (size_t)batch) {
@@ -435,13 +154,13 @@ static int ntt_batch_local(int field, unsigned log_n, int inverse, unsigned batc
         hipStream_t up = l->aux[0], down = l->aux[1];
         for (unsigned b = 0; b < batch; ++b) {
             uint8_t* d = (uint8_t*)buf + b * bytes;
-            PLK_TRY(lane_h2d(*l, d, in[b], bytes, up));  // >= 1 MiB: direct, or in chunks where the runtime rejects that (host_lane.h)
+            PLK_TRY(lane_h2d(*l, d, in[b * step], bytes, up));  // >= 1 MiB: direct, or in chunks where the runtime rejects that (host_lane.h)
             PLK_HIP_TRY(hipEventRecord(l->ev_ready[2 * b], up));
             PLK_HIP_TRY(hipStreamWaitEvent(l->stream, l->ev_ready[2 * b], 0));
             PLK_TRY(ntt_dev_impl(field, log_n, inverse, 1, d, d, l->stream));
             PLK_HIP_TRY(hipEventRecord(l->ev_ready[2 * b + 1], l->stream));
             PLK_HIP_TRY(hipStreamWaitEvent(down, l->ev_ready[2 * b + 1], 0));
-            PLK_TRY(lane_d2h(*l, c.outs, out[b], d, bytes, down));
+            PLK_TRY(lane_d2h(*l, c.outs, out[b * step], d, bytes, down));
         }
     }
     PLK_TRY(lane_join(*l));  // before the registrations and the device buffer go
@@ -469,16 +188,8 @@ int plk_ntt_batch(int field, unsigned log_n, int inverse, unsigned batch, const 
     if (!in || !out) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     for (unsigned b = 0; b < batch; ++b)
         if (!in[b] || !out[b]) return set_error(PLK_ERR_INVALID_ARG, "null pointer in batch slot %u", b);
-    return deal_units(log_n, batch, [&](unsigned first, unsigned step) -> int {
-        if (step == 1) return ntt_batch_local(field, log_n, inverse, batch, in, out);
-        std::vector<const uint64_t*> mi;
-        std::vector<uint64_t*> mo;
-        for (unsigned b = first; b < batch; b += step) {
-            mi.push_back(in[b]);
-            mo.push_back(out[b]);
-        }
-        return ntt_batch_local(field, log_n, inverse, (unsigned)mi.size(), mi.data(), mo.data());
-    });
+    return deal_units(log_n, batch,
+                      [&](unsigned first, unsigned step) -> int { return ntt_batch_local(field, log_n, inverse, batch, in, out, first, step); });
 }
 
 int plk_ntt(int field, unsigned log_n, int inverse, const uint64_t* in, uint64_t* out) {
@@ -493,12 +204,15 @@ int plk_ntt_padded_dev(int field, unsigned log_n, unsigned batch, const void* d_
     return ntt_padded_dev_impl(field, log_n, batch, d_in, in_len, in_stride, d_out, as_stream(stream));
 }
 
-static int ntt_padded_batch_local(int field, unsigned log_n, unsigned batch, const uint64_t* const* in, const size_t* n_in, uint64_t* const* out) {
-    if (batch == 0) return PLK_OK;
+static int ntt_padded_batch_local(int field, unsigned log_n, unsigned total, const uint64_t* const* in, const size_t* n_in, uint64_t* const* out,
+                                  unsigned first, unsigned step) {  // the share of a device: as in ntt_batch_local
+    if (first >= total) return PLK_OK;
+    const unsigned batch = (total - first + step - 1) / step;
+    in += first, n_in += first, out += first;
     const size_t n = (size_t)1 << log_n;
     size_t max_in = 0;
     for (unsigned b = 0; b < batch; ++b)
-        if (n_in[b] > max_in) max_in = n_in[b];
+        if (n_in[b * step] > max_in) max_in = n_in[b * step];
     LaneCall c;
     PLK_TRY(c.begin());
     void *din = nullptr, *dout = nullptr;
@@ -507,16 +221,18 @@ static int ntt_padded_batch_local(int field, unsigned log_n, unsigned batch, con
     PLK_TRY(c.tmp(dout, n * EB * batch));
     for (unsigned b = 0; b < batch; ++b) {
         uint8_t* slot = (uint8_t*)din + (size_t)b * max_in * EB;
-        // in place (out[b] == in[b]): ONE registration of the larger range, made here
-        c.pin(in[b], (const void*)out[b] == (const void*)in[b] && n > n_in[b] ? n * EB : n_in[b] * EB);
-        PLK_TRY(lane_h2d(*c.l, slot, in[b], n_in[b] * EB));
+        const uint64_t* src = in[b * step];
+        const size_t len = n_in[b * step];
+        // in place (out == in): ONE registration of the larger range, made here
+        c.pin(src, (const void*)out[b * step] == (const void*)src && n > len ? n * EB : len * EB);
+        PLK_TRY(lane_h2d(*c.l, slot, src, len * EB));
         // shorter polynomials of the batch: F::ZERO is all-zero limbs in Montgomery form too
-        if (n_in[b] < max_in) PLK_HIP_TRY(hipMemsetAsync(slot + n_in[b] * EB, 0, (max_in - n_in[b]) * EB, c.stream()));
+        if (len < max_in) PLK_HIP_TRY(hipMemsetAsync(slot + len * EB, 0, (max_in - len) * EB, c.stream()));
     }
     PLK_TRY(ntt_padded_dev_impl(field, log_n, batch, din, max_in, max_in, dout, c.stream()));
     for (unsigned b = 0; b < batch; ++b) {
-        c.pin(out[b], n * EB);  // in place: inside the registration made above
-        PLK_TRY(c.out(out[b], (uint8_t*)dout + (size_t)b * n * EB, n * EB));
+        c.pin(out[b * step], n * EB);  // in place: inside the registration made above
+        PLK_TRY(c.out(out[b * step], (uint8_t*)dout + (size_t)b * n * EB, n * EB));
     }
     return c.finish();
 }
@@ -532,18 +248,8 @@ int plk_ntt_padded_batch(int field, unsigned log_n, unsigned batch, const uint64
         if (n_in[b] > n) return set_error(PLK_ERR_INVALID_ARG, "n_in[%u] = %zu exceeds 2^%u", b, n_in[b], log_n);
         if ((n_in[b] && !in[b]) || !out[b]) return set_error(PLK_ERR_INVALID_ARG, "null pointer in batch slot %u", b);
     }
-    return deal_units(log_n, batch, [&](unsigned first, unsigned step) -> int {
-        if (step == 1) return ntt_padded_batch_local(field, log_n, batch, in, n_in, out);
-        std::vector<const uint64_t*> mi;
-        std::vector<size_t> ml;
-        std::vector<uint64_t*> mo;
-        for (unsigned b = first; b < batch; b += step) {
-            mi.push_back(in[b]);
-            ml.push_back(n_in[b]);
-            mo.push_back(out[b]);
-        }
-        return ntt_padded_batch_local(field, log_n, (unsigned)mi.size(), mi.data(), ml.data(), mo.data());
-    });
+    return deal_units(log_n, batch,
+                      [&](unsigned first, unsigned step) -> int { return ntt_padded_batch_local(field, log_n, batch, in, n_in, out, first, step); });
 }
 
 int plk_ntt_padded(int field, unsigned log_n, const uint64_t* in, size_t n_in, uint64_t* out) {
@@ -758,12 +464,8 @@ int plk_plonk_permutation_z(int field, unsigned log_degree, const uint64_t* wire
     PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
     PLK_TRY(plonk_permutation_z_dev_impl(field, log_degree, dw, ds, 1, k_is, beta, gamma, dout, dst, c.stream()));
     uint32_t st[2] = {0, 0};
-    PLK_TRY(c.out(st, dst, sizeof(st)));
-    PLK_TRY(c.sync());
-    if (st[0]) {
-        c.done = true;
-        return set_error(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plonk_util.rs:259)", st[0]);
-    }
+    PLK_TRY(c.read(st, dst, sizeof(st)));
+    if (st[0]) return c.refuse(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plonk_util.rs:259)", st[0]);
     PLK_TRY(c.out(out, dout, row));
     if (wraps_to_one) *wraps_to_one = (int)st[1];
     return c.finish();
@@ -796,12 +498,8 @@ int plk_plookup_grand_product(unsigned log_size, int field, const uint64_t* f, c
     PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
     PLK_TRY(plookup_grand_product_dev_impl(log_size, field, df, dt, ds, beta, gamma, dout, dst, c.stream()));
     uint32_t st[2] = {0, 0};
-    PLK_TRY(c.out(st, dst, sizeof(st)));
-    PLK_TRY(c.sync());
-    if (st[0]) {
-        c.done = true;
-        return set_error(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plookup.rs:191)", st[0]);
-    }
+    PLK_TRY(c.read(st, dst, sizeof(st)));
+    if (st[0]) return c.refuse(PLK_ERR_INVALID_ARG, "No inverse: %u of the denominators of rows 0..n-2 are zero (plookup.rs:191)", st[0]);
     PLK_TRY(c.out(out, dout, row));
     if (closes) *closes = (int)st[1];
     return c.finish();
@@ -852,13 +550,9 @@ int plk_plookup_sorted_multiset(unsigned log_size, int field, const uint64_t* f,
     PLK_TRY(c.tmp(dst, 2 * sizeof(uint32_t)));
     PLK_TRY(plookup_sorted_multiset_dev_impl(log_size, field, df, dt, ds, dst, c.stream()));
     uint32_t st[2] = {0, 0};
-    PLK_TRY(c.out(st, dst, sizeof(st)));
-    PLK_TRY(c.sync());
+    PLK_TRY(c.read(st, dst, sizeof(st)));
     if (missing) *missing = st[0];
-    if (st[0]) {
-        c.done = true;
-        return set_error(PLK_ERR_INVALID_ARG, "called `Option::unwrap()` on a `None` value: %u rows of f are not in t (plookup.rs:173)", st[0]);
-    }
+    if (st[0]) return c.refuse(PLK_ERR_INVALID_ARG, "called `Option::unwrap()` on a `None` value: %u rows of f are not in t (plookup.rs:173)", st[0]);
     PLK_TRY(c.out(s, ds, 2 * row - 32));
     return c.finish();
 }
@@ -892,15 +586,11 @@ int plk_plonk_sigma(unsigned log_degree, int field, const uint32_t* members, con
     PLK_TRY(c.tmp(dst, 3 * sizeof(uint32_t)));
     PLK_TRY(plonk_sigma_dev_impl(log_degree, field, dm, dof, num_partitions, num_members, k_is, dsig, dval, dst, c.stream()));
     uint32_t st[3] = {0, 0, 0};
-    PLK_TRY(c.out(st, dst, sizeof(st)));
-    PLK_TRY(c.sync());
-    if (st[0] || st[1] || st[2]) {
-        c.done = true;
-        if (st[2]) return set_error(PLK_ERR_INVALID_ARG, "wire id out of range: %u members are not below 9 n", st[2]);
-        if (st[1])
-            return set_error(PLK_ERR_INVALID_ARG, "Non-routed wires should not be in a partition containing other wires: %u of them are (partition.rs:94-98)", st[1]);
-        return set_error(PLK_ERR_INVALID_ARG, "no entry found for key: %u routed wires are not listed exactly once (partition.rs:109)", st[0]);
-    }
+    PLK_TRY(c.read(st, dst, sizeof(st)));
+    if (st[2]) return c.refuse(PLK_ERR_INVALID_ARG, "wire id out of range: %u members are not below 9 n", st[2]);
+    if (st[1])
+        return c.refuse(PLK_ERR_INVALID_ARG, "Non-routed wires should not be in a partition containing other wires: %u of them are (partition.rs:94-98)", st[1]);
+    if (st[0]) return c.refuse(PLK_ERR_INVALID_ARG, "no entry found for key: %u routed wires are not listed exactly once (partition.rs:109)", st[0]);
     if (sigma) PLK_TRY(c.out(sigma, dsig, n6 * 4));
     if (s_sigma) PLK_TRY(c.out(s_sigma, dval, n6 * 32));
     return c.finish();
@@ -1069,19 +759,13 @@ int plk_msm_precompute_ex(int curve, size_t n, const uint64_t* bases_xy, const u
         DeviceScope primary(0);
         return msm_precompute_multi(curve, n, bases_xy, base_zero, true, window_bits, nullptr, out_ctx);
     }
-    HostLane* l = nullptr;
-    PLK_TRY(lane_get(l));
-    LaneBuf db, dz;
-    PLK_TRY(db.alloc(n * 2 * L * 8, l->stream));
-    PLK_TRY(lane_h2d(*l, db.p, bases_xy, n * 2 * L * 8));
-    if (base_zero) {
-        PLK_TRY(dz.alloc(n, l->stream));
-        PLK_TRY(lane_h2d(*l, dz.p, base_zero, n));
-    }
-    const int rc = msm_precompute_dev_impl(curve, n, db.p, base_zero ? dz.p : nullptr, window_bits, flags, l->stream, out_ctx);  // synchronises the stream on success
-    if (rc != PLK_OK) (void)hipStreamSynchronize(l->stream);  // an early error return leaves the staged copies in flight
-    l->pin_used = 0;
-    return rc;
+    LaneCall c;  // registers nothing: the generators are uploaded once per context
+    PLK_TRY(c.begin());
+    void *db = nullptr, *dz = nullptr;
+    PLK_TRY(c.in(db, bases_xy, n * 2 * L * 8));
+    PLK_TRY(c.in_opt(dz, base_zero, n));
+    PLK_TRY(msm_precompute_dev_impl(curve, n, db, dz, window_bits, flags, c.stream(), out_ctx));  // synchronises the stream on success
+    return c.finish();  // one more synchronisation of the then idle stream: accepted in a precomputation
 }
 int plk_msm_precompute(int curve, size_t n, const uint64_t* bases_xy, const uint8_t* base_zero, unsigned window_bits, plk_msm_ctx** out_ctx) {
     PLK_API;
@@ -1241,10 +925,10 @@ int plk_curve_sum_affine(int curve, size_t k, const uint64_t* pts_xy, const uint
     PLK_TRY(c.begin());
     void *dp = nullptr, *dz = nullptr, *dxy = nullptr, *doz = nullptr;
     PLK_TRY(c.in(dp, pts_xy, k * 2 * L * 8));
-    if (pts_zero) PLK_TRY(c.in(dz, pts_zero, k));
+    PLK_TRY(c.in_opt(dz, pts_zero, k));
     PLK_TRY(c.tmp(dxy, 2 * L * 8));
     PLK_TRY(c.tmp(doz, 1));
-    PLK_TRY(curve_sum_affine_dev_impl(curve, k, dp, pts_zero ? dz : nullptr, dxy, doz, c.stream()));
+    PLK_TRY(curve_sum_affine_dev_impl(curve, k, dp, dz, dxy, doz, c.stream()));
     PLK_TRY(c.out(out_xy, dxy, 2 * L * 8));
     PLK_TRY(c.out(out_zero, doz, 1));
     return c.finish();
@@ -1281,10 +965,10 @@ int plk_msm_precompute_table(int curve, size_t n, const uint64_t* bases_xy, cons
     c.pin(out_xy, n * digits * 2 * L * 8);
     void *db = nullptr, *dz = nullptr, *dout = nullptr, *doz = nullptr;
     PLK_TRY(c.in(db, bases_xy, n * 2 * L * 8));
-    if (base_zero) PLK_TRY(c.in(dz, base_zero, n));
+    PLK_TRY(c.in_opt(dz, base_zero, n));
     PLK_TRY(c.tmp(dout, n * digits * 2 * L * 8));
     PLK_TRY(c.tmp(doz, n * digits));
-    PLK_TRY(msm_reference_table_dev_impl(curve, n, db, base_zero ? dz : nullptr, w, dout, doz, c.stream()));
+    PLK_TRY(msm_reference_table_dev_impl(curve, n, db, dz, w, dout, doz, c.stream()));
     PLK_TRY(c.out(out_xy, dout, n * digits * 2 * L * 8));
     PLK_TRY(c.out(out_zero, doz, n * digits));
     return c.finish();
@@ -1311,11 +995,11 @@ int plk_curve_fold_pairs(int curve, size_t m, const uint64_t* lo_xy, const uint8
     void *dlo = nullptr, *dhi = nullptr, *dlz = nullptr, *dhz = nullptr, *dout = nullptr, *doz = nullptr;
     PLK_TRY(c.in(dlo, lo_xy, pb));
     PLK_TRY(c.in(dhi, hi_xy, pb));
-    if (lo_zero) PLK_TRY(c.in(dlz, lo_zero, m));
-    if (hi_zero) PLK_TRY(c.in(dhz, hi_zero, m));
+    PLK_TRY(c.in_opt(dlz, lo_zero, m));
+    PLK_TRY(c.in_opt(dhz, hi_zero, m));
     PLK_TRY(c.tmp(dout, pb));
     PLK_TRY(c.tmp(doz, m));
-    PLK_TRY(curve_fold_pairs_dev_impl(curve, m, dlo, lo_zero ? dlz : nullptr, dhi, hi_zero ? dhz : nullptr, scalar_lo, scalar_hi, dout, doz, c.stream()));
+    PLK_TRY(curve_fold_pairs_dev_impl(curve, m, dlo, dlz, dhi, dhz, scalar_lo, scalar_hi, dout, doz, c.stream()));
     PLK_TRY(c.out(out_xy, dout, pb));
     PLK_TRY(c.out(out_zero, doz, m));
     return c.finish();
@@ -1341,12 +1025,8 @@ static int batch_inverse_host(int field, const uint64_t* x, uint64_t* out, uint8
     PLK_HIP_TRY(hipMemsetAsync(dc, 0, 4, c.stream()));
     PLK_TRY(field_batch_inverse_dev_impl(field, dx, dx, dz, (unsigned*)dc, count, c.stream()));
     unsigned zeros = 0;
-    PLK_TRY(c.out(&zeros, dc, 4));
-    PLK_TRY(c.sync());
-    if (strict && zeros) {
-        c.done = true;
-        return set_error(PLK_ERR_INVALID_ARG, "No inverse: %u of the %zu elements are zero (field.rs:266)", zeros, count);
-    }
+    PLK_TRY(c.read(&zeros, dc, 4));
+    if (strict && zeros) return c.refuse(PLK_ERR_INVALID_ARG, "No inverse: %u of the %zu elements are zero (field.rs:266)", zeros, count);
     PLK_TRY(c.out(out, dx, count * L * 8));
     if (is_none) PLK_TRY(c.out(is_none, dz, count));
     return c.finish();
@@ -1371,10 +1051,10 @@ int plk_curve_batch_to_affine(int curve, size_t count, const uint64_t* proj_xyz,
     PLK_TRY(c.begin());
     void *dp = nullptr, *dz = nullptr, *dxy = nullptr, *doz = nullptr;
     PLK_TRY(c.in(dp, proj_xyz, count * 3 * L * 8));
-    if (proj_zero) PLK_TRY(c.in(dz, proj_zero, count));
+    PLK_TRY(c.in_opt(dz, proj_zero, count));
     PLK_TRY(c.tmp(dxy, count * 2 * L * 8));
     PLK_TRY(c.tmp(doz, count));
-    PLK_TRY(curve_batch_to_affine_dev_impl(curve, count, dp, proj_zero ? dz : nullptr, dxy, doz, c.stream()));
+    PLK_TRY(curve_batch_to_affine_dev_impl(curve, count, dp, dz, dxy, doz, c.stream()));
     PLK_TRY(c.out(out_xy, dxy, count * 2 * L * 8));
     PLK_TRY(c.out(out_zero, doz, count));
     return c.finish();
@@ -1428,9 +1108,9 @@ int plk_curve_point_to_bytes(int curve, const uint64_t* xy, const uint8_t* zero,
     PLK_TRY(c.begin());
     void *dp = nullptr, *dz = nullptr, *db = nullptr;
     PLK_TRY(c.in(dp, xy, count * 2 * L * 8));
-    if (zero) PLK_TRY(c.in(dz, zero, count));
+    PLK_TRY(c.in_opt(dz, zero, count));
     PLK_TRY(c.tmp(db, count * rec));
-    PLK_TRY(point_bytes_impl(curve, 0, dp, zero ? dz : nullptr, count, db, nullptr, nullptr, c.stream()));
+    PLK_TRY(point_bytes_impl(curve, 0, dp, dz, count, db, nullptr, nullptr, c.stream()));
     PLK_TRY(c.out(out_bytes, db, count * rec));
     return c.finish();
 }
@@ -1678,7 +1358,7 @@ static int scalar_mul_host(size_t count, int curve, unsigned security_bits, size
     void *ds = nullptr, *dp = nullptr, *dz = nullptr, *dout = nullptr, *doz = nullptr;
     PLK_TRY(c.in(ds, scalars, n_scalars * 32));
     PLK_TRY(c.in(dp, p_xy, n_points * pt));
-    if (p_zero) PLK_TRY(c.in(dz, p_zero, n_points));
+    PLK_TRY(c.in_opt(dz, p_zero, n_points));
     PLK_TRY(c.tmp(dout, count * pt));
     PLK_TRY(c.tmp(doz, count));
     if (security_bits) PLK_TRY(halo_n_mul_dev_impl(count, curve, security_bits, n_scalars, ds, n_points, dp, dz, dout, doz, c.stream()));
@@ -1757,24 +1437,16 @@ int plk_halo_begin(int curve, size_t n, const uint64_t* halo_a, const uint64_t* 
     const int L = curve_limbs(curve);
     if (L < 0) return set_error(PLK_ERR_INVALID_ARG, "bad curve id %d", curve);
     if (!halo_a || !halo_b || !halo_g_xy) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
-    HostLane* l = nullptr;
-    PLK_TRY(lane_get(l));
-    LaneBuf da, db, dg, dz;
-    PLK_TRY(da.alloc(n * 32, l->stream));
-    PLK_TRY(db.alloc(n * 32, l->stream));
-    PLK_TRY(dg.alloc(n * 2 * L * 8, l->stream));
-    PLK_TRY(lane_h2d(*l, da.p, halo_a, n * 32));
-    PLK_TRY(lane_h2d(*l, db.p, halo_b, n * 32));
-    PLK_TRY(lane_h2d(*l, dg.p, halo_g_xy, n * 2 * L * 8));
-    if (halo_g_zero) {
-        PLK_TRY(dz.alloc(n, l->stream));
-        PLK_TRY(lane_h2d(*l, dz.p, halo_g_zero, n));
-    }
+    LaneCall c;  // registers nothing
+    PLK_TRY(c.begin());
+    void *da = nullptr, *db = nullptr, *dg = nullptr, *dz = nullptr;
+    PLK_TRY(c.in(da, halo_a, n * 32));
+    PLK_TRY(c.in(db, halo_b, n * 32));
+    PLK_TRY(c.in(dg, halo_g_xy, n * 2 * L * 8));
+    PLK_TRY(c.in_opt(dz, halo_g_zero, n));
     // the context works on the lane's stream from here on (one host thread per context)
-    const int rc = halo_begin_dev_impl(curve, n, da.p, db.p, dg.p, halo_g_zero ? dz.p : nullptr, pedersen_h_xy, u_prime_xy, freeze_log, l->stream, out_ctx);
-    (void)hipStreamSynchronize(l->stream);
-    l->pin_used = 0;
-    return rc;
+    PLK_TRY(halo_begin_dev_impl(curve, n, da, db, dg, dz, pedersen_h_xy, u_prime_xy, freeze_log, c.stream(), out_ctx));
+    return c.finish();
 }
 int plk_halo_round_lr(plk_halo_ctx* ctx, const uint64_t* l_blinding, const uint64_t* r_blinding, uint64_t* lr_xy, uint8_t* lr_zero) {
     PLK_API;
@@ -1795,6 +1467,7 @@ int plk_halo_free(plk_halo_ctx* ctx) {
 }
 
 // ---- self-test ----
+// (this entry, plk_curve_op, plk_msm_debug_digits and plk_curve_gen_bases_dev keep DevBuf and blocking copies: their impls take no stream)
 int plk_selftest_quad(int curve, const uint64_t* pts_xy, size_t n, unsigned quads, unsigned* mismatches) {
     PLK_API;
     const int L = curve_limbs(curve);

@@ -12,11 +12,19 @@
 
 #include "../../include/plonky_hip.h"
 #include "dispatch.cuh"
+#include "host_only.h"
 #include "table_cache.h"
+
+struct plk_msm_ctx;
+struct plk_halo_ctx;
 
 namespace plk {
 
-// thread-local error text behind plk_last_error()
+// Every function one translation unit defines and another calls is declared ONCE, here or in a header this one includes, and the
+// defining unit sees that declaration too: a return type or a default argument that diverges does not compile
+// (tests/test_capi_symbols.py keeps prototypes out of the .hip / .cpp files).
+
+// thread-local error text behind plk_last_error() (host_runtime.hip)
 std::string& last_error_ref();
 int set_error(int code, const char* fmt, ...);
 
@@ -268,7 +276,88 @@ struct MsmParts {
     const uint32_t* bucket_parts = nullptr;  // (absent, 0 or 1: every bucket)
 };
 
-// properties of an id, read from the parameter structs through the dispatchers (capi.hip); PLK_ERR_INVALID_ARG for an unknown id
+// ---- msm.hip: contexts ----
+int msm_precompute_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned window_bits, unsigned flags, hipStream_t stream,
+                            plk_msm_ctx** out_ctx, const void* d_extra = nullptr, size_t n_extra = 0, const size_t* also_n = nullptr,
+                            int also_count = 0);
+int msm_rebind_dev_impl(plk_msm_ctx* ctx, size_t n, const void* d_bases, const void* d_zero, const void* d_extra, size_t n_extra, hipStream_t stream);
+int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars, size_t n_scalars, void* d_out_xy, void* d_out_zero, hipStream_t stream,
+                         hipEvent_t* ready = nullptr, const MsmParts* parts = nullptr, unsigned out_flags = 0);
+int msm_reserve_workspaces_impl(plk_msm_ctx* ctx, unsigned count, hipStream_t stream);
+size_t msm_ctx_len(const plk_msm_ctx* ctx);
+unsigned msm_ctx_window(const plk_msm_ctx* ctx);
+int msm_ctx_curve(const plk_msm_ctx* ctx);
+int msm_ctx_is_comb(const plk_msm_ctx* ctx);
+int msm_ctx_table_free(const plk_msm_ctx* ctx);
+int msm_ctx_device(const plk_msm_ctx* ctx);
+std::vector<plk_msm_ctx*>& msm_ctx_peers(plk_msm_ctx* ctx);
+std::vector<plk_msm_ctx*>& msm_ctx_shards(plk_msm_ctx* ctx);
+void msm_ctx_delete(plk_msm_ctx* ctx);
+int msm_set_profiling_impl(plk_msm_ctx* ctx, int enable);
+int msm_get_timings_impl(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
+int msm_table_digits(int curve, unsigned w);
+int msm_reference_table_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned w, void* d_out_xy, void* d_out_zero,
+                                 hipStream_t stream);
+int msm_debug_digits_impl(int curve, unsigned window_bits, size_t n, const void* d_scalars, void* d_digits, hipStream_t stream);
+int msm_debug_digit_count(int curve, unsigned window_bits);
+// comb.hip: small fixed-base MSMs without buckets (a table of every multiple a signed 4-bit digit can ask for)
+struct CombPlan;
+int comb_build(int curve, size_t n, const void* d_base0, const void* d_chain, hipStream_t stream, CombPlan** out);
+void comb_free(CombPlan* p);
+int comb_execute(const CombPlan* p, unsigned batch, const void* const* d_scalars, const uint64_t* first, const uint64_t* count, void* d_out_xy, void* d_out_zero,
+                 hipStream_t stream);
+// msm_acc.hip, msm_order.hip, plookup_sort.hip: the checked build's guard counters
+int checked_build_impl();
+int checked_failures_impl(unsigned* counts);
+int msm_order_checked_failures(unsigned* counts);
+int plookup_sort_checked_failures(unsigned* counts);
+// multi.hip: a context over every device of the group
+void multi_plan_slot(int world, unsigned batch, size_t n, int d, unsigned slot, unsigned* vec, size_t* first, size_t* count);
+bool msm_ctx_is_multi(plk_msm_ctx* ctx);
+void group_copy_stats(unsigned long long* peer, unsigned long long* staged);
+int msm_precompute_multi(int curve, size_t n, const void* bases, const void* zero, bool host_src, unsigned window_bits, hipStream_t caller_stream,
+                         plk_msm_ctx** out_ctx);
+int msm_execute_multi(plk_msm_ctx* ctx, unsigned batch, const void* const* vecs, bool host_src, size_t n, void* d_out_xy, void* d_out_zero,
+                      hipStream_t caller_stream);
+// curve_ops.hip
+int msm_affine_to_projective_impl(int curve, unsigned batch, const void* d_xy, const void* d_zero, void* d_xyz, hipStream_t stream);
+int curve_sum_affine_dev_impl(int curve, size_t k, const void* d_pts, const void* d_zero, void* d_out_xy, void* d_out_zero, hipStream_t stream);
+size_t msm_partials_bytes(int curve, unsigned slots);
+int msm_combine_partials_dev_impl(int curve, unsigned world, unsigned batch, unsigned whole_per_rank, const void* d_gathered, void* d_out_xy, void* d_out_zero,
+                                  hipStream_t stream);
+int selftest_quad_dev_impl(int curve, const void* d_pts, uint32_t n, uint32_t quads, uint32_t* counts);
+int curve_op_dev_impl(int curve, int op, unsigned param, uint32_t count, const void* d_a_xy, const void* d_a_zero, const void* d_a_lambda, const void* d_b_xy,
+                      const void* d_b_zero, const void* d_b_lambda, const void* d_flags, void* d_out_xy, void* d_out_zero, void* d_mismatch);
+int curve_gen_bases_dev_impl(int curve, size_t n, uint64_t first, const void* d_g0d, void* d_out, hipStream_t stream);
+// fold.hip
+int curve_fold_pairs_dev_impl(int curve, size_t m, const void* d_lo, const void* d_lo_zero, const void* d_hi, const void* d_hi_zero,
+                              const uint64_t* a_mont, const uint64_t* b_mont, void* d_out_xy, void* d_out_zero, hipStream_t stream,
+                              const void* d_scalars = nullptr, int plus_lo = 0);
+int curve_fold_multi_dev_impl(int curve, size_t n_out, int r_bits, const void* d_g, const void* d_gz, const void* d_ratios, void* d_out_xy,
+                              void* d_out_zero, hipStream_t stream);
+// halo.hip: one inner-product argument
+int halo_begin_dev_impl(int curve, size_t n, const void* d_a, const void* d_b, const void* d_g, const void* d_gz, const uint64_t* h_xy,
+                        const uint64_t* u_xy, unsigned freeze_log, hipStream_t stream, plk_halo_ctx** out, plk_msm_ctx* tables = nullptr,
+                        unsigned lead_rounds = 0, size_t h_index = (size_t)-1, size_t u_index = (size_t)-1, const uint64_t* u_prime_scalar = nullptr);
+int halo_round_lr_impl(plk_halo_ctx* c, const uint64_t* l_blind, const uint64_t* r_blind, uint64_t* lr_xy, uint8_t* lr_zero);
+int halo_round_fold_impl(plk_halo_ctx* c, const uint64_t* u_j, const uint64_t* u_j_inv);
+size_t halo_len_impl(const plk_halo_ctx* c);
+int halo_frozen_impl(const plk_halo_ctx* c);
+int halo_read_impl(plk_halo_ctx* c, uint64_t* a, uint64_t* b, uint64_t* g_xy, uint8_t* g_zero);
+void halo_delete(plk_halo_ctx* c);
+// fieldops.hip, ceilings.hip, ntt.hip, poly.hip
+int field_op_impl(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
+int bench_ceilings_impl(double* out, unsigned n_out);
+int ntt_set_profiling_impl(int enable);
+int ntt_get_timings_impl(double* sum_ms, unsigned* launches);
+int poly_divide_by_z_h_dev_impl(int field, const void* d_coeffs, size_t len, size_t n, void* d_out, size_t out_cap, size_t* out_len,
+                                hipStream_t stream);
+int poly_mul_dev_impl(int field, const void* d_a, size_t la, const void* d_b, size_t lb, void* d_out, size_t out_cap, size_t* out_len,
+                      hipStream_t stream);
+int ntt_padded_dev_impl(int field, unsigned log_n, unsigned batch, const void* d_in, size_t in_len, size_t in_stride, void* d_out,
+                        hipStream_t stream);
+
+// properties of an id, read from the parameter structs through the dispatchers (host_runtime.hip); PLK_ERR_INVALID_ARG for an unknown id
 int field_limbs(int field);         // 64-bit limbs of an element
 int curve_limbs(int curve);         // ... of a coordinate
 int curve_scalar_field(int curve);  // PLK_FIELD_* of the scalars

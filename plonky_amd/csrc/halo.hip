@@ -40,32 +40,7 @@
 #include "fp.cuh"
 #include "field_params.cuh"
 
-struct plk_msm_ctx;
-
 namespace plk {
-
-int msm_precompute_dev_impl(int curve, size_t n, const void* d_bases, const void* d_zero, unsigned window_bits, unsigned flags, hipStream_t stream,
-                            plk_msm_ctx** out_ctx, const void* d_extra = nullptr, size_t n_extra = 0, const size_t* also_n = nullptr,
-                            int also_count = 0);
-int msm_rebind_dev_impl(plk_msm_ctx* ctx, size_t n, const void* d_bases, const void* d_zero, const void* d_extra, size_t n_extra, hipStream_t stream);
-int msm_execute_dev_impl(plk_msm_ctx* ctx, unsigned batch, const void* d_scalars, size_t n_scalars, void* d_out_xy, void* d_out_zero, hipStream_t stream,
-                         hipEvent_t* ready = nullptr, const MsmParts* parts = nullptr, unsigned out_flags = 0);
-int msm_reserve_workspaces_impl(plk_msm_ctx* ctx, unsigned count, hipStream_t stream);
-// hostnorm.cpp: ProjectivePoint::to_affine on the host for `count` points (x | y | z -> x | y)
-int host_projective_to_affine(int curve, unsigned count, const uint8_t* xyz, const uint8_t* zero, uint8_t* xy);
-void msm_ctx_delete(plk_msm_ctx* ctx);
-int curve_fold_pairs_dev_impl(int curve, size_t m, const void* d_lo, const void* d_lo_zero, const void* d_hi, const void* d_hi_zero,
-                              const uint64_t* a_mont, const uint64_t* b_mont, void* d_out_xy, void* d_out_zero, hipStream_t stream,
-                              const void* d_scalars = nullptr, int plus_lo = 0);
-int curve_fold_multi_dev_impl(int curve, size_t n_out, int r_bits, const void* d_g, const void* d_gz, const void* d_ratios, void* d_out_xy,
-                              void* d_out_zero, hipStream_t stream);
-size_t msm_ctx_len(const plk_msm_ctx* ctx);
-int msm_ctx_curve(const plk_msm_ctx* ctx);
-int msm_ctx_table_free(const plk_msm_ctx* ctx);
-int msm_ctx_is_comb(const plk_msm_ctx* ctx);
-size_t msm_partials_bytes(int curve, unsigned slots);
-int msm_combine_partials_dev_impl(int curve, unsigned world, unsigned batch, unsigned whole_per_rank, const void* d_gathered, void* d_out_xy, void* d_out_zero,
-                                  hipStream_t stream);
 
 constexpr int HALO_PART_BLOCKS = 256;
 struct HaloScalar {

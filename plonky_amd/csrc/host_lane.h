@@ -1,5 +1,5 @@
 // host_lane.h -- the host-pointer entry points' plumbing: one lane per (calling thread, device).
-// Shared by capi.hip (the extern "C" surface) and multi.hip (the fan-out over the devices of a group).
+// Shared by capi.hip (the extern "C" surface), multi.hip (the fan-out over the devices of a group) and host_runtime.hip (the lanes).
 //
 // The reference calls the hot path from Rayon workers (plonk_util.rs:173-189: nine transforms / commitments at once).  Every
 // host thread that enters through a host-pointer entry point owns a lane per device it works on: non-blocking streams of its own,
@@ -26,9 +26,10 @@ constexpr size_t DIRECT_MIN = (size_t)64 << 10;    // larger pieces are copied s
 constexpr size_t BOUNCE_BYTES = (size_t)256 << 10;  // chunk of a copy the runtime would not take straight from / to the caller's memory
 constexpr int LANE_AUX = 2;
 
-// the route a copy from / to the caller's memory took, counted process-wide (capi.hip; read by the tests through plk_internal_host_stats)
+// the route a copy from / to the caller's memory took, counted process-wide (host_runtime.hip; read by the tests through plk_internal_host_stats)
 enum LaneRoute : int { LANE_STAGED = 0, LANE_DIRECT, LANE_BOUNCED, LANE_ROUTES };
 void lane_count(int route);
+int host_stats(unsigned long long* out, unsigned n);  // the registry's branch counts, waits, rechecks, then the copies per route
 
 struct HostLane {
     hipStream_t stream = nullptr;
@@ -88,7 +89,7 @@ inline int lane_join(HostLane& l) {
 }
 
 // Caller buffers registered with the HIP runtime so that copies from / to them are asynchronous: a process-wide registry of
-// NON-OVERLAPPING intervals, each with a hold count per thread (capi.hip).  Two threads that pass the same read-only buffer at the
+// NON-OVERLAPPING intervals, each with a hold count per thread (host_runtime.hip).  Two threads that pass the same read-only buffer at the
 // same time (the Rayon-style callers the lanes are built for) share ONE registration, released by whoever finishes last.  A request
 // that extends or partly overlaps a registered interval never leaves a half-registered range: it waits for other threads' holds to
 // end, or - the calling thread's own holds - re-registers the union after synchronising the devices.  Registration can still fail
@@ -257,12 +258,20 @@ struct LaneCall {
         PLK_TRY(tmp(d, bytes));
         return lane_h2d(*l, d, h, bytes);
     }
+    // an optional input (the zero flags of a point array): no host pointer, no device buffer - d stays null
+    int in_opt(void*& d, const void* h, size_t bytes) { return h ? in(d, h, bytes) : PLK_OK; }
     int out(void* h, const void* d, size_t bytes) { return lane_d2h(*l, outs, h, d, bytes); }
-    int sync() {  // results of the kernels so far are needed on the host before the call goes on
-        PLK_TRY(lane_finish(*l, outs));
-        return PLK_OK;
+    int sync() { return lane_finish(*l, outs); }  // results of the kernels so far are needed on the host before the call goes on
+    // the status words of the kernels, on the host when this returns
+    int read(void* h, const void* d, size_t bytes) {
+        PLK_TRY(out(h, d, bytes));
+        return sync();
     }
-    bool done = false;
+    // the call ends on what read() brought back: nothing is in flight any more, the destructor need not synchronise again
+    template <class... A> int refuse(int code, const char* fmt, A... a) {
+        done = true;
+        return set_error(code, fmt, a...);
+    }
     int finish() {
         done = true;
         return lane_finish(*l, outs);
@@ -276,6 +285,9 @@ struct LaneCall {
         }
         pins.clear();  // only now: every copy from / to the registered ranges has completed
     }
+
+  private:
+    bool done = false;
 };
 
 }  // namespace plk

@@ -7,6 +7,7 @@
 
 #include "ec.cuh"
 #include "fp.cuh"
+#include "host_only.h"
 
 namespace plk {
 

@@ -43,23 +43,6 @@
 
 namespace plk {
 
-// comb.hip: small fixed-base MSMs without buckets (a table of every multiple a signed 4-bit digit can ask for)
-struct CombPlan;
-int comb_build(int curve, size_t n, const void* d_base0, const void* d_chain, hipStream_t stream, CombPlan** out);
-void comb_free(CombPlan* p);
-int comb_execute(const CombPlan* p, unsigned batch, const void* const* d_scalars, const uint64_t* first, const uint64_t* count, void* d_out_xy, void* d_out_zero,
-                 hipStream_t stream);
-// msm_acc.hip: the bucket accumulation kernel (its own translation unit)
-template <class C> int msm_accumulate_blocks_per_cu();
-template <class C>
-void msm_launch_accumulate(unsigned blocks, hipStream_t stream, const void* tab, const void* sorted, const void* off, void* p_start, void* p_head,
-                           void* head_live, void* head_bucket, void* live_list, uint32_t* live_count, uint32_t buckets, const uint32_t* dyn_chunk, int wshift,
-                           uint32_t n_sub, uint32_t tab_entries);
-// msm_order.hip: digits + the two-level bucket ordering; msm_tail.hip: the reduction
-template <class C> int msm_launch_glv_split(const void* d_scalars, size_t n, void* halves, hipStream_t stream);
-template <class C> int msm_launch_order_stage(int stage, const OrdCfg& o, const OrdBuffers& b, hipStream_t stream);
-template <class C> int msm_launch_digits(const void* d_scalars, size_t n, const OrdCfg& o, void* d_digits, hipStream_t stream);
-template <class C> int msm_launch_reduce_stage(int stage, const TailGeom& g, const TailBatch& tb, hipStream_t stream);
 constexpr size_t COMB_MAX_N = (size_t)1 << 15;  // generators up to which a tabled context with an automatic window is a comb (1 GB of table at 2^15)
 constexpr size_t COMB_AUTO_MAX_N = (size_t)1 << 12;  // ... and up to which it is chosen without being asked for (measured faster than the bucket method)
 constexpr int COMB_WINDOW = 4, COMB_WINDOWS = 64;

@@ -311,8 +311,6 @@ PLK_FOR_EACH_CURVE(PLK_ACC_INSTANTIATE)
 #undef PLK_ACC_INSTANTIATE
 
 // ---- the checked build (-DPLK_CHECKED: msm_acc_checked.o + msm_order_checked.o; include/plonky_hip.h) ----
-int msm_order_checked_failures(unsigned* counts);  // msm_order.hip
-int plookup_sort_checked_failures(unsigned* counts);  // plookup_sort.hip
 PLK_CHK_READER(msm_acc_checked_failures)
 int checked_build_impl() {
 #ifdef PLK_CHECKED

@@ -100,6 +100,20 @@ struct OrdBuffers {
     uint32_t* meta;  // META_* (msm_geom.h)
     uint32_t chunk, lanes, buckets;
 };
+
+// the launchers msm.hip calls, instantiated per curve by the unit that holds the kernels
+// msm_acc.hip: the bucket accumulation kernel
+template <class C> int msm_accumulate_blocks_per_cu();
+template <class C>
+void msm_launch_accumulate(unsigned blocks, hipStream_t stream, const void* tab, const void* sorted, const void* off, void* p_start, void* p_head,
+                           void* head_live, void* head_bucket, void* live_list, uint32_t* live_count, uint32_t buckets, const uint32_t* dyn_chunk, int wshift,
+                           uint32_t n_sub, uint32_t tab_entries);
+// msm_order.hip: digits + the two-level bucket ordering; msm_tail.hip: the reduction
+template <class C> int msm_launch_glv_split(const void* d_scalars, size_t n, void* halves, hipStream_t stream);
+template <class C> int msm_launch_order_stage(int stage, const OrdCfg& o, const OrdBuffers& b, hipStream_t stream);
+template <class C> int msm_launch_digits(const void* d_scalars, size_t n, const OrdCfg& o, void* d_digits, hipStream_t stream);
+template <class C> int msm_launch_reduce_stage(int stage, const TailGeom& g, const TailBatch& tb, hipStream_t stream);
+
 // the guard counters of a translation unit (-DPLK_CHECKED), read back for plk_checked_failures
 #ifdef PLK_CHECKED
 #define PLK_CHK_READER(fn)                                                                        \

@@ -39,10 +39,6 @@ struct PdivArg {  // host words of the call: -b' (R-form, zeros above k) and the
     uint32_t factor[8];
 };
 
-// host-only field work of a call (polydiv_host.cpp)
-int host_pdiv_prepare(int field, const uint64_t* b, size_t lb, uint64_t* negb, uint64_t* factor);
-int host_poly_from_roots(int field, unsigned k, const uint64_t* roots, uint64_t* out);
-
 template <class P> PLK_DI Fz<P> pdiv_shfl(const Fz<P>& v, int src) {
     Fz<P> r;
 #pragma unroll

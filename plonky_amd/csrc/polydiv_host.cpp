@@ -5,6 +5,7 @@
 
 #include "dispatch.cuh"
 #include "fp.cuh"
+#include "host_only.h"
 
 namespace plk {
 
