@@ -52,32 +52,94 @@ def log2_strict(n):  # util.rs:12-19 (panics when n is not a power of two)
     return r
 
 
-def init_devices(n_devices=0):
-    """Run the host-pointer entry points over several GPUs from this one process (plk_init_devices): 0 = PLK_NGPU or every
-    visible device; with PLK_VIRTUAL_DEVICES=k, k logical devices on one physical GPU.  Returns the number of logical devices."""
-    L = _lib.load()
-    _lib.check(L.plk_init_devices(int(n_devices)))
-    return int(L.plk_device_count())
-
-
-def device_count():
-    return int(_lib.load().plk_device_count())
-
-
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
+# ---- the marshalling and error layer: every wrapper below is its shapes, its outputs and one _call ----
 def _u64(x, *shape):
     """host limbs as a contiguous uint64 array, of that shape when one is given"""
     a = np.ascontiguousarray(x, dtype=np.uint64)
     return a.reshape(*shape) if shape else a
 
 
+def _as(dtype, x, *shape):
+    """_u64 for the other dtypes (flags and bytes, wire ids); None stays None"""
+    if x is None:
+        return None
+    a = np.ascontiguousarray(x, dtype=dtype)
+    return a.reshape(*shape) if shape else a
+
+
+def _u8(x, *shape):
+    return _as(np.uint8, x, *shape)
+
+
+# Limb counts.  An id outside the tables is a KeyError in Python, EXCEPT in the four wrappers that ask with strict=False (rescue_mds,
+# RescueContext, hash_usize_to_curve, kth_root): those shape their arrays with 4 limbs and leave the refusal to the library.  The
+# wrappers that never look a count up (4-limb scalars, entries that exist for the 4-limb fields only) send a bad id on as well.
+def _field_limbs(field, strict=True):
+    return _FIELD_LIMBS[field] if strict else _FIELD_LIMBS.get(field, 4)
+
+
+def _curve_limbs(curve, strict=True):
+    return _CURVE_LIMBS[curve] if strict else _CURVE_LIMBS.get(curve, 4)
+
+
 def _elems(field, a):
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    L = _FIELD_LIMBS[field]
-    return a.reshape(-1, L)
+    return _u64(a, -1, _FIELD_LIMBS[field])
+
+
+def _points(curve, generators):
+    return _u64(generators, -1, 2, _CURVE_LIMBS[curve])
+
+
+def _scalar(x):
+    """one scalar: 4 limbs whatever the curve"""
+    return _u64(x, 4)
+
+
+def _scalars(x):
+    return _u64(x, -1, 4)
+
+
+def _ptr(a):
+    """the host pointer of an array; None for None"""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _ptrs(arrays, null_empty=False):
+    """a ctypes array of the host pointers of these arrays (or of one array's rows); null_empty: an array with nothing in it is a
+    null entry, and the array itself never has length 0"""
+    if null_empty:
+        return (ctypes.c_void_p * max(1, len(arrays)))(*[a.ctypes.data if a.size else None for a in arrays])
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+_NO_INVERSE = ("No inverse", "No inverse")  # field.rs:266 and the Div of field.rs: the reference's panic, as _call takes it
+
+
+def _call(rc, panics=(), message=None, refusal=False):
+    """The one status check.  A PLK_ERR_INVALID_ARG whose text starts with one of `panics` is a panic of the reference: AssertionError
+    (explicit, so it survives python -O) with `message`, or with the library's text when there is none.  refusal: any other
+    PLK_ERR_INVALID_ARG is ValueError(text).  Everything else is lib.check's PlonkyHipError."""
+    if rc == _lib.PLK_OK:
+        return
+    if rc == _lib.PLK_ERR_INVALID_ARG and (panics or refusal):
+        text = _lib.load().plk_last_error().decode("utf-8", "replace")
+        if panics and text.startswith(panics):
+            raise AssertionError(text if message is None else message)
+        if refusal:
+            raise ValueError(text)
+    _lib.check(rc)
+
+
+def init_devices(n_devices=0):
+    """Run the host-pointer entry points over several GPUs from this one process (plk_init_devices): 0 = PLK_NGPU or every
+    visible device; with PLK_VIRTUAL_DEVICES=k, k logical devices on one physical GPU.  Returns the number of logical devices."""
+    L = _lib.load()
+    _call(L.plk_init_devices(int(n_devices)))
+    return int(L.plk_device_count())
+
+
+def device_count():
+    return int(_lib.load().plk_device_count())
 
 
 class FftPrecomputation:
@@ -96,7 +158,7 @@ class FftPrecomputation:
 def fft_precompute(field, degree):
     degree_pow = log2_ceil(degree)
     assert degree_pow <= _TWO_ADICITY[field], "n_power <= TWO_ADICITY"  # field.rs:430
-    _lib.check(_lib.load().plk_ntt_precompute(field, degree_pow))
+    _call(_lib.load().plk_ntt_precompute(field, degree_pow))
     return FftPrecomputation(field, degree_pow)
 
 
@@ -106,14 +168,14 @@ def fft_precompute_table(field, degree):
     Bls12377Base)."""
     degree_pow = log2_ceil(degree)
     assert degree_pow <= _TWO_ADICITY[field], "n_power <= TWO_ADICITY"  # field.rs:430
-    flat = np.empty(((2 << degree_pow) - 1, _FIELD_LIMBS[field]), dtype=np.uint64)
-    _lib.check(_lib.load().plk_ntt_precompute_table(field, degree_pow, _ptr(flat)))
+    flat = np.empty(((2 << degree_pow) - 1, _field_limbs(field)), dtype=np.uint64)
+    _call(_lib.load().plk_ntt_precompute_table(field, degree_pow, _ptr(flat)))
     return [flat[(1 << i) - 1: (2 << i) - 1] for i in range(degree_pow + 1)]
 
 
 def _ntt(field, log_n, inverse, x):
     out = np.empty_like(x)
-    _lib.check(_lib.load().plk_ntt(field, log_n, 1 if inverse else 0, _ptr(x), _ptr(out)))
+    _call(_lib.load().plk_ntt(field, log_n, 1 if inverse else 0, _ptr(x), _ptr(out)))
     return out
 
 
@@ -139,7 +201,7 @@ def fft_with_precomputation(coefficients, precomputation):
     if degree == 1 << log_n:
         return fft_with_precomputation_power_of_2(x, precomputation)
     out = np.empty((1 << log_n, x.shape[1]), dtype=np.uint64)
-    _lib.check(_lib.load().plk_ntt_padded(precomputation.field, log_n, _ptr(x), degree, _ptr(out)))
+    _call(_lib.load().plk_ntt_padded(precomputation.field, log_n, _ptr(x), degree, _ptr(out)))
     return out
 
 
@@ -151,13 +213,11 @@ def fft(field, coefficients):
 def fft_batch(field, polys, inverse=False):
     """`batch` independent power-of-two transforms in one call (the par_iter over the 9 wire
     polynomials, plonk_util.rs:169-190).  polys: (batch, n, 4)."""
-    polys = np.ascontiguousarray(polys, dtype=np.uint64)
+    polys = _u64(polys)
     batch, n = polys.shape[0], polys.shape[1]
     log_n = log2_strict(n)
     out = np.empty_like(polys)
-    ins = (ctypes.c_void_p * batch)(*[polys[b].ctypes.data for b in range(batch)])
-    outs = (ctypes.c_void_p * batch)(*[out[b].ctypes.data for b in range(batch)])
-    _lib.check(_lib.load().plk_ntt_batch(field, log_n, 1 if inverse else 0, batch, ins, outs))
+    _call(_lib.load().plk_ntt_batch(field, log_n, 1 if inverse else 0, batch, _ptrs(polys), _ptrs(out)))
     return out
 
 
@@ -175,7 +235,7 @@ def polynomial_divide_by_z_h(field, coeffs, n):
     cap = max(x.shape[0], _pow2_ceil(x.shape[0]))
     out = np.zeros((cap, x.shape[1]), dtype=np.uint64)
     out_len = ctypes.c_size_t(0)
-    _lib.check(_lib.load().plk_poly_divide_by_z_h(field, _ptr(x), x.shape[0], n, _ptr(out), cap, ctypes.byref(out_len)))
+    _call(_lib.load().plk_poly_divide_by_z_h(field, _ptr(x), x.shape[0], n, _ptr(out), cap, ctypes.byref(out_len)))
     return out[: out_len.value].copy()
 
 
@@ -185,7 +245,7 @@ def polynomial_mul(field, a, b):
     cap = _pow2_ceil(x.shape[0] + y.shape[0])
     out = np.zeros((cap, x.shape[1]), dtype=np.uint64)
     out_len = ctypes.c_size_t(0)
-    _lib.check(_lib.load().plk_poly_mul(field, _ptr(x), x.shape[0], _ptr(y), y.shape[0], _ptr(out), cap, ctypes.byref(out_len)))
+    _call(_lib.load().plk_poly_mul(field, _ptr(x), x.shape[0], _ptr(y), y.shape[0], _ptr(out), cap, ctypes.byref(out_len)))
     return out[: out_len.value].copy()
 
 
@@ -196,6 +256,11 @@ def _degree_plus_one(x):
     """Polynomial::degree_plus_one (polynomial.rs:107-112): 0 for the zero polynomial"""
     nz = np.nonzero(x.any(axis=1))[0]
     return int(nz[-1]) + 1 if nz.size else 0
+
+
+def _division_buffers(x, y, da, db):
+    """the trimmed operands and the quotient and remainder buffers of a division with deg a >= deg b >= 1"""
+    return _u64(x[:da]), _u64(y[:db]), np.empty((da - db + 1, 4), dtype=np.uint64), np.empty((db - 1, 4), dtype=np.uint64)
 
 
 def polynomial_division(field, a, b):
@@ -217,10 +282,8 @@ def polynomial_division(field, a, b):
         return field_op(field, "mul", x, np.repeat(inv, x.shape[0], axis=0)), empty
     if db - 1 > POLY_DIV_MAX_DEGREE:
         raise ValueError("divisor of degree %d: at most %d (PLK_POLY_DIV_MAX_DEGREE)" % (db - 1, POLY_DIV_MAX_DEGREE))
-    xs, ys = np.ascontiguousarray(x[:da]), np.ascontiguousarray(y[:db])
-    q = np.empty((da - db + 1, 4), dtype=np.uint64)
-    r = np.empty((db - 1, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_poly_division(field, _ptr(xs), da, _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
+    xs, ys, q, r = _division_buffers(x, y, da, db)
+    _call(_lib.load().plk_poly_division(field, _ptr(xs), da, _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
     return q, r[: _degree_plus_one(r)].copy()
 
 
@@ -231,7 +294,7 @@ def polynomial_inv_mod_xn(field, h, n):
     if not x[0].any():
         raise ValueError("Inverse doesn't exist.")
     out = np.empty((n, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_poly_inv_mod_xn(n, field, _ptr(x), x.shape[0], _ptr(out)))
+    _call(_lib.load().plk_poly_inv_mod_xn(n, field, _ptr(x), x.shape[0], _ptr(out)))
     return out
 
 
@@ -244,10 +307,8 @@ def polynomial_div_rem(field, a, b):
     da, db = _degree_plus_one(x), _degree_plus_one(y)
     if db == 0 or da < db or db == 1:
         return polynomial_division(field, x, y)  # no divisor degree is involved in these branches
-    xs, ys = np.ascontiguousarray(x[:da]), np.ascontiguousarray(y[:db])
-    q = np.empty((da - db + 1, 4), dtype=np.uint64)
-    r = np.empty((db - 1, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_poly_div_rem(da, field, _ptr(xs), _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
+    xs, ys, q, r = _division_buffers(x, y, da, db)
+    _call(_lib.load().plk_poly_div_rem(da, field, _ptr(xs), _ptr(ys), db, _ptr(q), q.shape[0], _ptr(r)))
     return q, r[: _degree_plus_one(r)].copy()
 
 
@@ -256,22 +317,21 @@ def polynomial_long_division(field, a, b):
     the loop and leaves the quotient at deg a + 1 coefficients."""
     x, y = _elems(field, a), _elems(field, b)
     if _degree_plus_one(y) == 1 and _degree_plus_one(x) >= 1:
-        q, r = polynomial_division(field, x[: _degree_plus_one(x)], y)
-        return q, r
+        return polynomial_division(field, x[: _degree_plus_one(x)], y)
     return polynomial_division(field, a, b)
 
 
 def polynomial_from_roots(field, roots):
     """prod_i (X - roots[i]) (the fold of plonk.rs:207-215) -> (k + 1, 4), monic; at most 32 roots."""
-    r = np.ascontiguousarray(roots, dtype=np.uint64).reshape(-1, 4)
+    r = _scalars(roots)
     out = np.empty((r.shape[0] + 1, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_poly_from_roots(field, r.shape[0], _ptr(r), _ptr(out)))
+    _call(_lib.load().plk_poly_from_roots(field, r.shape[0], _ptr(r), _ptr(out)))
     return out
 
 
 def scale_polynomials(field, polys, alpha, degree):
     """scale_polynomials (plonk_util.rs:283-298): sum_j alpha^j polys[j], the first `degree` coefficients: powers + reduce_polynomials."""
-    polys = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+    polys = [_scalars(p) for p in polys]
     assert all(p.shape[0] >= degree for p in polys), "the reference indexes every polynomial up to degree"
     return reduce_polynomials(field, [p[:degree] for p in polys], powers(field, alpha, len(polys)), degree)
 
@@ -289,10 +349,8 @@ def polynomials_to_values_padded(polys, precomputation):
     out = np.empty((batch, n, 4), dtype=np.uint64)
     if batch == 0:
         return out
-    ins = (ctypes.c_void_p * batch)(*[p.ctypes.data for p in ps])
     lens = (ctypes.c_size_t * batch)(*[p.shape[0] for p in ps])
-    outs = (ctypes.c_void_p * batch)(*[out[b].ctypes.data for b in range(batch)])
-    _lib.check(_lib.load().plk_ntt_padded_batch(field, precomputation.degree_pow, batch, ins, lens, outs))
+    _call(_lib.load().plk_ntt_padded_batch(field, precomputation.degree_pow, batch, _ptrs(ps), lens, _ptrs(out)))
     return out
 
 
@@ -331,12 +389,6 @@ class MsmPrecomputation:
             pass
 
 
-def _points(curve, generators):
-    L = _CURVE_LIMBS[curve]
-    g = np.ascontiguousarray(generators, dtype=np.uint64).reshape(-1, 2, L)
-    return g
-
-
 MSM_TABLE_FREE = 1  # PLK_MSM_TABLE_FREE
 
 
@@ -347,25 +399,25 @@ def msm_precompute(curve, generators, w, zero=None, device_window=0, table_free=
     table_free: no window tables on the device (generators used once: msm_parallel, the IPA rounds)."""
     g = _points(curve, generators)
     n = g.shape[0]
-    z = None
-    if zero is not None:
-        z = np.ascontiguousarray(zero, dtype=np.uint8)
-        assert z.shape[0] == n
+    z = _u8(zero)
+    assert z is None or z.shape[0] == n
     ctx = ctypes.c_void_p()
-    _lib.check(_lib.load().plk_msm_precompute_ex(curve, n, _ptr(g), _ptr(z) if z is not None else None, device_window,
-                                                 MSM_TABLE_FREE if table_free else 0, ctypes.byref(ctx)))
+    _call(_lib.load().plk_msm_precompute_ex(curve, n, _ptr(g), _ptr(z), device_window, MSM_TABLE_FREE if table_free else 0, ctypes.byref(ctx)))
     return MsmPrecomputation(curve, ctx, n, w)
 
 
-def msm_execute_parallel(precomputation, scalars):
-    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+def _msm_execute(entry, rows, precomputation, scalars):
+    s = _scalars(scalars)
     # assert_eq!(precomputation.powers_per_generator.len(), scalars.len())  curve_msm.rs:106
     assert s.shape[0] == precomputation.n, "powers_per_generator.len() != scalars.len()"
-    L = _CURVE_LIMBS[precomputation.curve]
-    out = np.zeros((2, L), dtype=np.uint64)
+    out = np.zeros((rows, _curve_limbs(precomputation.curve)), dtype=np.uint64)
     oz = np.zeros(1, dtype=np.uint8)
-    _lib.check(_lib.load().plk_msm_execute(precomputation._ctx, _ptr(s), s.shape[0], _ptr(out), _ptr(oz)))
+    _call(getattr(_lib.load(), entry)(precomputation._ctx, _ptr(s), s.shape[0], _ptr(out), _ptr(oz)))
     return out, int(oz[0])
+
+
+def msm_execute_parallel(precomputation, scalars):
+    return _msm_execute("plk_msm_execute", 2, precomputation, scalars)
 
 
 # msm_execute (serial, curve_msm.rs:63) computes the same group element as msm_execute_parallel.
@@ -375,26 +427,18 @@ msm_execute = msm_execute_parallel
 def msm_execute_parallel_projective(precomputation, scalars):
     """msm_execute_parallel with its OWN return type (curve_msm.rs:102-157 returns the ProjectivePoint `y`, not normalised):
     ((3, L) x | y | z Montgomery limbs, zero flag).  ProjectivePoint::to_affine / batch_to_affine (curve.rs:206-232) gives the unique point."""
-    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
-    assert s.shape[0] == precomputation.n, "powers_per_generator.len() != scalars.len()"
-    L = _CURVE_LIMBS[precomputation.curve]
-    out = np.zeros((3, L), dtype=np.uint64)
-    oz = np.zeros(1, dtype=np.uint8)
-    _lib.check(_lib.load().plk_msm_execute_projective(precomputation._ctx, _ptr(s), s.shape[0], _ptr(out), _ptr(oz)))
-    return out, int(oz[0])
+    return _msm_execute("plk_msm_execute_projective", 3, precomputation, scalars)
 
 
 def msm_execute_batch(precomputation, scalar_vectors):
     """commit_polynomials (plonk_util.rs:215-231): several scalar vectors, same generators."""
-    sv = np.ascontiguousarray(scalar_vectors, dtype=np.uint64)
+    sv = _u64(scalar_vectors)
     batch = sv.shape[0]
     sv = sv.reshape(batch, -1, 4)
     assert sv.shape[1] == precomputation.n, "powers_per_generator.len() != scalars.len()"
-    L = _CURVE_LIMBS[precomputation.curve]
-    out = np.zeros((batch, 2, L), dtype=np.uint64)
+    out = np.zeros((batch, 2, _curve_limbs(precomputation.curve)), dtype=np.uint64)
     oz = np.zeros(batch, dtype=np.uint8)
-    ptrs = (ctypes.c_void_p * batch)(*[sv[b].ctypes.data for b in range(batch)])
-    _lib.check(_lib.load().plk_msm_execute_batch(precomputation._ctx, batch, ptrs, sv.shape[1], _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_msm_execute_batch(precomputation._ctx, batch, _ptrs(sv), sv.shape[1], _ptr(out), _ptr(oz)))
     return out, oz
 
 
@@ -411,10 +455,10 @@ def coeffs_vec_to_commitments(precomputation, coefficients_vec, blinding_factors
     """poly_commit.rs:51-66: one commitment per coefficient vector, pedersen_hash(coeffs) + [r] H, already normalised
     (the reference's batch_to_affine).  blinding_factors: one Montgomery scalar per vector (zeros when blinding is off).
     precomputation: from commitment_precompute.  Returns (points (k, 2, L), zero flags (k,))."""
-    cv = np.ascontiguousarray(coefficients_vec, dtype=np.uint64)
+    cv = _u64(coefficients_vec)
     k = cv.shape[0]
     cv = cv.reshape(k, -1, 4)
-    r = np.ascontiguousarray(blinding_factors, dtype=np.uint64).reshape(k, 1, 4)
+    r = _u64(blinding_factors, k, 1, 4)
     assert cv.shape[1] + 1 == precomputation.n, "coefficients.len() must equal the number of generators (curve_msm.rs:106)"
     return msm_execute_batch(precomputation, np.concatenate([cv, r], axis=1))
 
@@ -432,14 +476,13 @@ def msm_precompute_table(curve, generators, w, zero=None):
     """The CONTENTS of the reference's MsmPrecomputation (curve_msm.rs:16-52): powers_per_generator[i][j] = [2^(w j)] G_i,
     j < ceil(ScalarField::BITS / w).  Returns (table (n, digits, 2, L), zero flags (n, digits))."""
     g = _points(curve, generators)
-    n = g.shape[0]
-    L = _CURVE_LIMBS[curve]
+    n, L = g.shape[0], g.shape[2]
     digits = int(_lib.load().plk_msm_table_digits(curve, w))
     assert digits > 0
-    z = None if zero is None else np.ascontiguousarray(zero, dtype=np.uint8)
+    z = _u8(zero)
     out = np.zeros((n, digits, 2, L), dtype=np.uint64)
     oz = np.zeros((n, digits), dtype=np.uint8)
-    _lib.check(_lib.load().plk_msm_precompute_table(curve, n, _ptr(g), _ptr(z) if z is not None else None, w, _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_msm_precompute_table(curve, n, _ptr(g), _ptr(z), w, _ptr(out), _ptr(oz)))
     return out, oz
 
 
@@ -450,26 +493,21 @@ def fold_generators(curve, g_lo, g_hi, scalar_lo, scalar_hi, lo_zero=None, hi_ze
     lo, hi = _points(curve, g_lo), _points(curve, g_hi)
     m = lo.shape[0]
     assert hi.shape[0] == m
-    a = np.ascontiguousarray(scalar_lo, dtype=np.uint64).reshape(4)
-    b = np.ascontiguousarray(scalar_hi, dtype=np.uint64).reshape(4)
-    lz = None if lo_zero is None else np.ascontiguousarray(lo_zero, dtype=np.uint8)
-    hz = None if hi_zero is None else np.ascontiguousarray(hi_zero, dtype=np.uint8)
+    a, b = _scalar(scalar_lo), _scalar(scalar_hi)
+    lz, hz = _u8(lo_zero), _u8(hi_zero)
     out = np.zeros_like(lo)
     oz = np.zeros(m, dtype=np.uint8)
-    _lib.check(_lib.load().plk_curve_fold_pairs(curve, m, _ptr(lo), _ptr(lz) if lz is not None else None, _ptr(hi),
-                                                _ptr(hz) if hz is not None else None, _ptr(a), _ptr(b), _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_curve_fold_pairs(curve, m, _ptr(lo), _ptr(lz), _ptr(hi), _ptr(hz), _ptr(a), _ptr(b), _ptr(out), _ptr(oz)))
     return out, oz
 
 
 def curve_sum_affine(curve, points, zero=None):
     """Adds k affine points (per-GPU partial MSM results after the all-gather)."""
     p = _points(curve, points)
-    k = p.shape[0]
-    z = None if zero is None else np.ascontiguousarray(zero, dtype=np.uint8)
-    L = _CURVE_LIMBS[curve]
-    out = np.zeros((2, L), dtype=np.uint64)
+    z = _u8(zero)
+    out = np.zeros((2, p.shape[2]), dtype=np.uint64)
     oz = np.zeros(1, dtype=np.uint8)
-    _lib.check(_lib.load().plk_curve_sum_affine(curve, k, _ptr(p), _ptr(z) if z is not None else None, _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_curve_sum_affine(curve, p.shape[0], _ptr(p), _ptr(z), _ptr(out), _ptr(oz)))
     return out, int(oz[0])
 
 
@@ -483,23 +521,21 @@ def affine_summation_best(curve, summation, zero=None):
 def affine_multisummation_best(curve, summations, zeros=None):
     """curve_summations.rs:24-35: k independent sums of affine points -> k points, one device sum per list (inside the MSM the
     reference's call site, curve_msm.rs:131-145, is replaced by the bucket accumulation - DESIGN.md section 5)."""
-    L = _CURVE_LIMBS[curve]
-    out = []
-    for k, pts in enumerate(summations):
-        arr = np.asarray(pts, dtype=np.uint64).reshape(-1, 2, L)
-        out.append(curve_sum_affine(curve, arr, None if zeros is None else zeros[k]))
-    return out
+    _curve_limbs(curve)  # a bad id is refused here, with no list as well
+    return [curve_sum_affine(curve, pts, None if zeros is None else zeros[k]) for k, pts in enumerate(summations)]
+
+
+FIELD_OPS = {"add": 0, "sub": 1, "mul": 2, "neg": 3, "square": 4, "inverse": 5, "to_canonical": 6, "from_canonical": 7,
+             "inverse_euclid": 8, "inverse_divsteps": 9, "inverse_divsteps_var": 10, "inverse_divsteps_one_lane": 11,
+             "mul_add2_edge": 12, "wide_sum": 13}
 
 
 def field_op(field, op, a, b=None):
     """Element-wise device field arithmetic (parity tests of the HIP field code)."""
-    ops = {"add": 0, "sub": 1, "mul": 2, "neg": 3, "square": 4, "inverse": 5, "to_canonical": 6, "from_canonical": 7,
-           "inverse_euclid": 8, "inverse_divsteps": 9, "inverse_divsteps_var": 10, "inverse_divsteps_one_lane": 11,
-           "mul_add2_edge": 12, "wide_sum": 13}
     a = _elems(field, a)
     out = np.empty_like(a)
-    bb = _elems(field, b) if b is not None else a
-    _lib.check(_lib.load().plk_field_op(field, ops[op], _ptr(a), _ptr(bb), _ptr(out), a.shape[0]))
+    bb = a if b is None else _elems(field, b)
+    _call(_lib.load().plk_field_op(field, FIELD_OPS[op], _ptr(a), _ptr(bb), _ptr(out), a.shape[0]))
     return out
 
 
@@ -511,18 +547,16 @@ def curve_op(curve, op, a, b=None, flags=None, param=0):
     """Element-wise device point arithmetic (plk_curve_op: parity tests of ecz.cuh / ecz_coop.cuh).  a, b: (points (n, 2, L), identity
     flags (n,) or None, lambdas (n, L)).  Returns (affine results (m, 2, L), zero flags (m,), mismatch word); m = ceil(n / param) for
     "wave_sum_q", n otherwise."""
-    L = _CURVE_LIMBS[curve]
-    u8 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.uint8)
-    axy, az, al = _u64(a[0], -1, 2, L), u8(a[1]), _u64(a[2], -1, L)
+    L = _curve_limbs(curve)
+    axy, az, al = _u64(a[0], -1, 2, L), _u8(a[1]), _u64(a[2], -1, L)
     n = axy.shape[0]
-    bxy, bz, bl = (None, None, None) if b is None else (_u64(b[0], n, 2, L), u8(b[1]), None if b[2] is None else _u64(b[2], n, L))
-    fl = np.zeros(n, dtype=np.uint8) if flags is None else u8(flags)
+    bxy, bz, bl = (None, None, None) if b is None else (_u64(b[0], n, 2, L), _u8(b[1]), None if b[2] is None else _u64(b[2], n, L))
+    fl = np.zeros(n, dtype=np.uint8) if flags is None else _u8(flags)
     code = CURVE_OPS[op]
     m = -(-n // param) if code == 7 else n
     out, oz, mism = np.zeros((m, 2, L), dtype=np.uint64), np.zeros(m, dtype=np.uint8), ctypes.c_uint(0xFFFFFFFF)
-    ptr = lambda x: None if x is None else _ptr(x)
-    _lib.check(_lib.load().plk_curve_op(curve, code, param, n, ptr(axy), ptr(az), ptr(al), ptr(bxy), ptr(bz), ptr(bl), ptr(fl), ptr(out), ptr(oz),
-                                        ctypes.byref(mism)))
+    _call(_lib.load().plk_curve_op(curve, code, param, n, _ptr(axy), _ptr(az), _ptr(al), _ptr(bxy), _ptr(bz), _ptr(bl), _ptr(fl), _ptr(out), _ptr(oz),
+                                   ctypes.byref(mism)))
     return out, oz, int(mism.value)
 
 
@@ -530,12 +564,11 @@ def msm_debug_digits(curve, scalars, window_bits):
     """The MSM's digit recoding on its own (to_digits, curve_msm.rs:159-180): scalars (n, 4) Montgomery limbs in the curve's scalar field
     -> (n, ceil((BITS + 1) / w)) signed digits as the ordering kernels form them, and the reference's unsigned digits rebuilt from them
     (u_j = d_j - carry_j + 2^w carry_(j+1), carry_(j+1) = [d_j - carry_j < 0]), and the carry out of the top window (always 0: it has room)."""
-    import ctypes
-    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    s = _scalars(scalars)
     nd = ctypes.c_uint()
-    _lib.check(_lib.load().plk_msm_debug_digits(curve, window_bits, 0, None, None, ctypes.byref(nd)))
+    _call(_lib.load().plk_msm_debug_digits(curve, window_bits, 0, None, None, ctypes.byref(nd)))
     d = np.zeros((s.shape[0], nd.value), dtype=np.int32)
-    _lib.check(_lib.load().plk_msm_debug_digits(curve, window_bits, s.shape[0], _ptr(s), _ptr(d), ctypes.byref(nd)))
+    _call(_lib.load().plk_msm_debug_digits(curve, window_bits, s.shape[0], _ptr(s), _ptr(d), ctypes.byref(nd)))
     # carry_(j+1) = [d_j - carry_j < 0]: a negative digit borrowed from the next window, and so did a ZERO digit that stands for
     # 2^w - 1 + carry_j = 2^w (the device has no entry for it: magnitude 0, carry out)
     unsigned = np.zeros(d.shape, dtype=np.int64)
@@ -554,13 +587,13 @@ NUM_WIRES, NUM_ROUTED_WIRES, NUM_CONSTANTS, GRID_WIDTH = 9, 6, 6, 65  # plonk.rs
 def evaluate_all_constraints(field, local_constant_values, local_wire_values, right_wire_values, below_wire_values, inner_zeta, inner_a):
     """gates/mod.rs:46-125 at `count` points: constants (count, 6, 4), wires (count, 9, 4) x 3 -> (count, 8, 4).
     inner_zeta / inner_a: InnerC::ZETA and InnerC::A (4 limbs, Montgomery) - how InnerC enters the curve gates."""
-    k = np.ascontiguousarray(local_constant_values, dtype=np.uint64).reshape(-1, NUM_CONSTANTS, 4)
-    l, r, b = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, NUM_WIRES, 4) for x in (local_wire_values, right_wire_values, below_wire_values))
+    k = _u64(local_constant_values, -1, NUM_CONSTANTS, 4)
+    l, r, b = (_u64(x, -1, NUM_WIRES, 4) for x in (local_wire_values, right_wire_values, below_wire_values))
     count = k.shape[0]
     assert l.shape[0] == r.shape[0] == b.shape[0] == count
-    zeta, a = (np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (inner_zeta, inner_a))
+    zeta, a = _scalar(inner_zeta), _scalar(inner_a)
     out = np.empty((count, 8, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_plonk_evaluate_all_constraints(field, count, _ptr(k), _ptr(l), _ptr(r), _ptr(b), _ptr(zeta), _ptr(a), _ptr(out)))
+    _call(_lib.load().plk_plonk_evaluate_all_constraints(field, count, _ptr(k), _ptr(l), _ptr(r), _ptr(b), _ptr(zeta), _ptr(a), _ptr(out)))
     return out
 
 
@@ -569,14 +602,14 @@ def vanishing_points(field, degree, constants_8n, wire_values_8n, s_sigma_values
     (ifft_with_precomputation_power_of_2) is the vanishing polynomial.  Tables: (6, 8n, 4), (9, 8n, 4), (6, 8n, 4), (8n, 4)."""
     log_degree = log2_strict(degree)
     n8 = 8 * degree
-    c = np.ascontiguousarray(constants_8n, dtype=np.uint64).reshape(NUM_CONSTANTS, n8, 4)
-    w = np.ascontiguousarray(wire_values_8n, dtype=np.uint64).reshape(NUM_WIRES, n8, 4)
-    s = np.ascontiguousarray(s_sigma_values_8n, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, n8, 4)
-    z = np.ascontiguousarray(plonk_z_points_8n, dtype=np.uint64).reshape(n8, 4)
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, 4)
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma, inner_zeta, inner_a)]
+    c = _u64(constants_8n, NUM_CONSTANTS, n8, 4)
+    w = _u64(wire_values_8n, NUM_WIRES, n8, 4)
+    s = _u64(s_sigma_values_8n, NUM_ROUTED_WIRES, n8, 4)
+    z = _u64(plonk_z_points_8n, n8, 4)
+    ks = _u64(k_is, NUM_ROUTED_WIRES, 4)
+    sc = [_scalar(x) for x in (alpha, beta, gamma, inner_zeta, inner_a)]
     out = np.empty((n8, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_plonk_vanishing_points(field, log_degree, _ptr(c), _ptr(w), _ptr(s), _ptr(z), _ptr(ks), *[_ptr(x) for x in sc], _ptr(out)))
+    _call(_lib.load().plk_plonk_vanishing_points(field, log_degree, _ptr(c), _ptr(w), _ptr(s), _ptr(z), _ptr(ks), *map(_ptr, sc), _ptr(out)))
     return out
 
 
@@ -589,15 +622,13 @@ def permutation_polynomial(field, degree, wire_values, s_sigma_values, k_is, bet
     assert sigma_stride in (1, 8), "sigma_stride must be 1 or 8"
     w = np.asarray(wire_values, dtype=np.uint64).reshape(-1, degree, 4)
     assert w.shape[0] >= NUM_ROUTED_WIRES
-    w = np.ascontiguousarray(w[:NUM_ROUTED_WIRES])
-    s = np.ascontiguousarray(s_sigma_values, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, degree * sigma_stride, 4)
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, 4)
-    b, g = (np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma))
+    w = _u64(w[:NUM_ROUTED_WIRES])  # the first six rows, then contiguous
+    s = _u64(s_sigma_values, NUM_ROUTED_WIRES, degree * sigma_stride, 4)
+    ks = _u64(k_is, NUM_ROUTED_WIRES, 4)
+    b, g = _scalar(beta), _scalar(gamma)
     out = np.empty((degree, 4), dtype=np.uint64)
-    rc = _lib.load().plk_plonk_permutation_z(field, log_degree, _ptr(w), _ptr(s), sigma_stride, _ptr(ks), _ptr(b), _ptr(g), _ptr(out), None)
-    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
-        raise AssertionError("No inverse")  # the reference panics (plonk_util.rs:259, field.rs Div)
-    _lib.check(rc)
+    # the reference panics (plonk_util.rs:259, field.rs Div)
+    _call(_lib.load().plk_plonk_permutation_z(field, log_degree, _ptr(w), _ptr(s), sigma_stride, _ptr(ks), _ptr(b), _ptr(g), _ptr(out), None), *_NO_INVERSE)
     return out
 
 
@@ -682,29 +713,21 @@ class WirePartitions:
         return np.array(members, dtype=np.uint32), offsets
 
 
-def _sigma_panic(rc):
-    """the reference's panics behind PLK_ERR_INVALID_ARG of plk_plonk_sigma -> AssertionError with the library's text"""
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        msg = _lib.load().plk_last_error().decode("utf-8", "replace")
-        if msg.startswith(("Non-routed wires", "no entry found for key", "wire id out of range")):
-            raise AssertionError(msg)
-    _lib.check(rc)
+_SIGMA_PANICS = ("Non-routed wires", "no entry found for key", "wire id out of range")  # the reference's panics behind plk_plonk_sigma
 
 
 def wire_partitions_to_sigma(field, degree, members, offsets, k_is, want_values=True):
     """to_sigma + sigma_polynomials through the device (plk_plonk_sigma; host arrays, copied through PCIe): members / offsets as
     WirePartitions.to_csr gives them, k_is (6, 4) -> (sigma (6 degree,) uint32, s_sigma (6, degree, 4)).  Where the reference panics
-    (a routed wire that is not listed exactly once, a non-routed wire in company) -> AssertionError."""
+    (a routed wire that is not listed exactly once, a non-routed wire in company) -> AssertionError with the library's text."""
     log_degree = log2_strict(degree)
-    m = np.ascontiguousarray(members, dtype=np.uint32).reshape(-1)
-    o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    m, o = _as(np.uint32, members, -1), _as(np.uint32, offsets, -1)
     assert o.shape[0] >= 1, "offsets holds num_partitions + 1 entries"
     assert int(o[-1]) == m.shape[0], "offsets[num_partitions] must be the number of members"
-    ks = np.ascontiguousarray(k_is, dtype=np.uint64).reshape(NUM_ROUTED_WIRES, 4)
+    ks = _u64(k_is, NUM_ROUTED_WIRES, 4)
     sigma = np.empty(NUM_ROUTED_WIRES * degree, dtype=np.uint32)
     values = np.empty((NUM_ROUTED_WIRES, degree, 4), dtype=np.uint64) if want_values else None
-    _sigma_panic(_lib.load().plk_plonk_sigma(log_degree, field, _ptr(m), _ptr(o), o.shape[0] - 1, _ptr(ks), _ptr(sigma),
-                                             _ptr(values) if want_values else None))
+    _call(_lib.load().plk_plonk_sigma(log_degree, field, _ptr(m), _ptr(o), o.shape[0] - 1, _ptr(ks), _ptr(sigma), _ptr(values)), _SIGMA_PANICS)
     return (sigma, values) if want_values else sigma
 
 
@@ -712,11 +735,11 @@ def sigma_polynomials(field, sigma, degree, k_is):
     """sigma_polynomials (plonk_util.rs:264-280): sigma, 6 degree entries below 6 degree -> (6, degree, 4), element (j, r) =
     k_is[x / degree] g^(x % degree) for x = sigma[j degree + r].  The values of the identity permutation come from the device
     (plk_plonk_sigma over singletons); sigma then picks among them."""
-    sg = np.ascontiguousarray(sigma, dtype=np.int64).reshape(-1)
+    sg = _as(np.int64, sigma, -1)
     n6 = NUM_ROUTED_WIRES * degree
     assert sg.shape[0] == n6 and (sg.size == 0 or (0 <= sg.min() and sg.max() < n6)), "sigma maps [6n] to [6n]"
     _, ident = wire_partitions_to_sigma(field, degree, np.arange(n6, dtype=np.uint32), np.arange(n6 + 1, dtype=np.uint32), k_is)
-    return np.ascontiguousarray(ident.reshape(n6, 4)[sg].reshape(NUM_ROUTED_WIRES, degree, 4))
+    return _u64(ident.reshape(n6, 4)[sg], NUM_ROUTED_WIRES, degree, 4)
 
 
 # ---- the Plookup prover's two loops (plookup/src/plookup.rs) ----
@@ -733,13 +756,12 @@ def plookup_sorted_multiset(f, t):
         keys = np.fromiter((pos[row.tobytes()] for row in s), dtype=np.int64, count=s.shape[0])
     except KeyError:
         raise AssertionError("called `Option::unwrap()` on a `None` value: an element of f is not in t")
-    return np.ascontiguousarray(s[np.argsort(keys, kind="stable")])
+    return _u64(s[np.argsort(keys, kind="stable")])
 
 
-def plookup_sorted_multiset_device(field, f, t):
-    """plookup_sorted_multiset through the device (plk_plookup_sorted_multiset; host arrays, copied through PCIe): f (N, 4) = f_padded
-    or the n = N - 1 values the reference passes, t (N, 4), N a power of two >= 2 -> (2 N - 1, 4).  An element of f that is not in t
-    makes the reference's unwrap() panic -> AssertionError."""
+def _plookup_f_t(field, f, t):
+    """t (N, 4), N a power of two, and f_padded: the n = N - 1 values the reference passes get the zero row that is not read
+    -> (log N, f (N, 4), t)"""
     ta = _elems(field, t)
     size = ta.shape[0]
     log_size = log2_strict(size)
@@ -747,12 +769,18 @@ def plookup_sorted_multiset_device(field, f, t):
     assert fa.shape[0] in (size - 1, size), "f has n or n + 1 rows"
     if fa.shape[0] == size - 1:
         fa = np.concatenate([fa, np.zeros((1, 4), dtype=np.uint64)])
-    out = np.empty((2 * size - 1, 4), dtype=np.uint64)
+    return log_size, fa, ta
+
+
+def plookup_sorted_multiset_device(field, f, t):
+    """plookup_sorted_multiset through the device (plk_plookup_sorted_multiset; host arrays, copied through PCIe): f (N, 4) = f_padded
+    or the n = N - 1 values the reference passes, t (N, 4), N a power of two >= 2 -> (2 N - 1, 4).  An element of f that is not in t
+    makes the reference's unwrap() panic -> AssertionError."""
+    log_size, fa, ta = _plookup_f_t(field, f, t)
+    out = np.empty((2 * ta.shape[0] - 1, 4), dtype=np.uint64)
     missing = ctypes.c_uint(0)
-    rc = _lib.load().plk_plookup_sorted_multiset(log_size, field, _ptr(fa), _ptr(ta), _ptr(out), ctypes.byref(missing))
-    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("called `Option::unwrap()`"):
-        raise AssertionError("called `Option::unwrap()` on a `None` value: %d elements of f are not in t" % missing.value)
-    _lib.check(rc)
+    _call(_lib.load().plk_plookup_sorted_multiset(log_size, field, _ptr(fa), _ptr(ta), _ptr(out), ctypes.byref(missing)),
+          "called `Option::unwrap()`", "called `Option::unwrap()` on a `None` value: %d elements of f are not in t" % missing.value)
     return out
 
 
@@ -760,51 +788,43 @@ def plookup_grand_polynomial(field, f, t, s, beta, gamma, return_closes=False):
     """grand_polynomial (plookup.rs:180-202): f (N, 4) = f_padded (or the n = N - 1 values the reference passes: the last row is not
     read), t (N, 4), s (2 N - 1, 4) -> the N values of Z, values[0] = values[N - 1] = 1.  A zero denominator in rows 0..n-2 panics in
     the reference ("No inverse") -> AssertionError.  return_closes: also whether the product over all n rows is 1 (f is in t)."""
-    ta = _elems(field, t)
+    log_size, fa, ta = _plookup_f_t(field, f, t)
     size = ta.shape[0]
-    log_size = log2_strict(size)
-    fa = _elems(field, f)
-    assert fa.shape[0] in (size - 1, size), "f has n or n + 1 rows"
-    if fa.shape[0] == size - 1:
-        fa = np.concatenate([fa, np.zeros((1, 4), dtype=np.uint64)])
     sa = _elems(field, s)
     assert sa.shape[0] == 2 * size - 1, "s has 2 n + 1 rows"
-    b, g = (np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (beta, gamma))
+    b, g = _scalar(beta), _scalar(gamma)
     out = np.empty((size, 4), dtype=np.uint64)
     closes = ctypes.c_int(0)
-    rc = _lib.load().plk_plookup_grand_product(log_size, field, _ptr(fa), _ptr(ta), _ptr(sa), _ptr(b), _ptr(g), _ptr(out), ctypes.byref(closes))
-    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
-        raise AssertionError("No inverse")  # the reference panics (plookup.rs:191, field.rs Div)
-    _lib.check(rc)
+    # the reference panics (plookup.rs:191, field.rs Div)
+    _call(_lib.load().plk_plookup_grand_product(log_size, field, _ptr(fa), _ptr(ta), _ptr(sa), _ptr(b), _ptr(g), _ptr(out), ctypes.byref(closes)), *_NO_INVERSE)
     return (out, bool(closes.value)) if return_closes else out
 
 
 def plookup_vanishing_values(field, values_4n, alpha, beta, gamma):
     """The 4(n+1)-point loop of vanishing_polynomial (plookup.rs:225-269): values_4n (5, 4 N, 4), rows z, f, t, h1, h2 on the 4N domain
     -> (4 N, 4); Polynomial::from_evaluations of the result is the vanishing polynomial."""
-    v = np.ascontiguousarray(values_4n, dtype=np.uint64)
+    v = _u64(values_4n)
     assert v.ndim == 3 and v.shape[0] == 5 and v.shape[2] == 4
     log_size = log2_strict(v.shape[1]) - 2
-    sc = [np.ascontiguousarray(x, dtype=np.uint64).reshape(4) for x in (alpha, beta, gamma)]
+    sc = [_scalar(x) for x in (alpha, beta, gamma)]
     out = np.empty((v.shape[1], 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_plookup_vanishing_points(log_size, field, _ptr(v), *[_ptr(x) for x in sc], _ptr(out)))
+    _call(_lib.load().plk_plookup_vanishing_points(log_size, field, _ptr(v), *map(_ptr, sc), _ptr(out)))
     return out
 
 
 # ---- the opening step (plonk.rs:261-308, halo.rs:38-44 and 143-155, plonk_util.rs:123-133 and 311-326) ----
 def _poly_args(polys):
     """list of (len, 4) limb arrays -> (kept arrays, ctypes array of host pointers, lengths)"""
-    arrs = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
-    ptrs = (ctypes.c_void_p * max(1, len(arrs)))(*[a.ctypes.data if a.shape[0] else None for a in arrs])
+    arrs = [_scalars(p) for p in polys]
     lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)  # size_t
-    return arrs, ptrs, lens
+    return arrs, _ptrs(arrs, null_empty=True), lens
 
 
 def powers(field, x, n):
     """powers (plonk_util.rs:123-133): [1, x, ..., x^(n-1)] as (n, 4)."""
-    xs = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+    xs = _scalar(x)
     out = np.empty((n, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_field_powers(field, _ptr(xs), n, _ptr(out)))
+    _call(_lib.load().plk_field_powers(field, _ptr(xs), n, _ptr(out)))
     return out
 
 
@@ -812,9 +832,9 @@ def eval_polys(field, polys, points):
     """open_all_polynomials (plonk.rs:459-482): out[k][i] = polys[i].eval_from_power(powers(points[k], len(polys[i]))), (n_points, n_polys, 4).
     polys: a list of (len, 4) coefficient arrays of any lengths; 1..8 points."""
     arrs, ptrs, lens = _poly_args(polys)
-    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+    pts = _scalars(points)
     out = np.empty((pts.shape[0], len(arrs), 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_plonk_eval_polys(field, len(arrs), ptrs, _ptr(lens), pts.shape[0], _ptr(pts), _ptr(out)))
+    _call(_lib.load().plk_plonk_eval_polys(field, len(arrs), ptrs, _ptr(lens), pts.shape[0], _ptr(pts), _ptr(out)))
     return out
 
 
@@ -822,32 +842,28 @@ def reduce_polynomials(field, polys, scalars, degree):
     """reduced_coeffs of batch_opening_proof (halo.rs:38-44): out[j] = sum_i scalars[i] * polys[i][j], (degree, 4); a polynomial longer
     than `degree` trips the reference's assertion -> AssertionError here."""
     arrs, ptrs, lens = _poly_args(polys)
-    sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    sc = _scalars(scalars)
     assert sc.shape[0] == len(arrs), "one scalar per polynomial"
     assert all(a.shape[0] <= degree for a in arrs), "polynomial longer than the degree"
     out = np.empty((degree, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_poly_reduce(field, len(arrs), ptrs, _ptr(lens), _ptr(sc), degree, _ptr(out)))
+    _call(_lib.load().plk_poly_reduce(field, len(arrs), ptrs, _ptr(lens), _ptr(sc), degree, _ptr(out)))
     return out
 
 
 def build_halo_b(field, points, v, degree):
     """build_halo_b (halo.rs:143-155): out[j] = sum_k v^k points[k]^j, (degree, 4)."""
-    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
-    vs = np.ascontiguousarray(v, dtype=np.uint64).reshape(4)
+    pts, vs = _scalars(points), _scalar(v)
     out = np.empty((degree, 4), dtype=np.uint64)
-    _lib.check(_lib.load().plk_halo_build_b(field, pts.shape[0], _ptr(pts), _ptr(vs), degree, _ptr(out)))
+    _call(_lib.load().plk_halo_build_b(field, pts.shape[0], _ptr(pts), _ptr(vs), degree, _ptr(out)))
     return out
 
 
 def halo_s(field, us):
     """halo_s (plonk_util.rs:311-326): the 2^k coefficients of g(X, us).  A zero challenge has no inverse: the reference panics
     ("No inverse", field.rs:266) -> AssertionError here."""
-    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    u = _scalars(us)
     out = np.empty((1 << u.shape[0], 4), dtype=np.uint64)
-    rc = _lib.load().plk_halo_s(field, u.shape[0], _ptr(u), _ptr(out))
-    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
-        raise AssertionError("No inverse")
-    _lib.check(rc)
+    _call(_lib.load().plk_halo_s(field, u.shape[0], _ptr(u), _ptr(out)), *_NO_INVERSE)
     return out
 
 
@@ -856,10 +872,7 @@ def batch_multiplicative_inverse(field, x):
     """Field::batch_multiplicative_inverse (field.rs:251-278): panics ("No inverse") on a zero element -> AssertionError here."""
     a = _elems(field, x)
     out = np.empty_like(a)
-    rc = _lib.load().plk_field_batch_inverse(field, _ptr(a), _ptr(out), a.shape[0])
-    if rc == _lib.PLK_ERR_INVALID_ARG and _lib.load().plk_last_error().decode("utf-8", "replace").startswith("No inverse"):
-        raise AssertionError("No inverse")  # the reference panics (field.rs:266); explicit, so it survives python -O
-    _lib.check(rc)
+    _call(_lib.load().plk_field_batch_inverse(field, _ptr(a), _ptr(out), a.shape[0]), *_NO_INVERSE)
     return out
 
 
@@ -868,19 +881,19 @@ def batch_multiplicative_inverse_opt(field, x):
     a = _elems(field, x)
     out = np.empty_like(a)
     none = np.zeros(a.shape[0], dtype=np.uint8)
-    _lib.check(_lib.load().plk_field_batch_inverse_opt(field, _ptr(a), _ptr(out), _ptr(none), a.shape[0]))
+    _call(_lib.load().plk_field_batch_inverse_opt(field, _ptr(a), _ptr(out), _ptr(none), a.shape[0]))
     return out, none
 
 
 def batch_to_affine(curve, proj_xyz, zero=None):
     """ProjectivePoint::batch_to_affine (curve.rs:216-232): (n, 3, L) homogeneous projective limbs (+ zero flags) -> ((n, 2, L), zero flags)."""
-    L = _CURVE_LIMBS[curve]
-    p = np.ascontiguousarray(proj_xyz, dtype=np.uint64).reshape(-1, 3, L)
+    L = _curve_limbs(curve)
+    p = _u64(proj_xyz, -1, 3, L)
     n = p.shape[0]
-    z = np.ascontiguousarray(zero, dtype=np.uint8) if zero is not None else None
+    z = _u8(zero)
     out = np.empty((n, 2, L), dtype=np.uint64)
     oz = np.zeros(n, dtype=np.uint8)
-    _lib.check(_lib.load().plk_curve_batch_to_affine(curve, n, _ptr(p), _ptr(z) if z is not None else None, _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_curve_batch_to_affine(curve, n, _ptr(p), _ptr(z), _ptr(out), _ptr(oz)))
     return out, oz
 
 
@@ -889,36 +902,32 @@ def field_to_bytes(field, x):
     """ToBytes for field elements: (n, BYTES) uint8, little-endian canonical value."""
     a = _elems(field, x)
     out = np.empty((a.shape[0], a.shape[1] * 8), dtype=np.uint8)
-    _lib.check(_lib.load().plk_field_to_bytes(field, _ptr(a), a.shape[0], _ptr(out)))
+    _call(_lib.load().plk_field_to_bytes(field, _ptr(a), a.shape[0], _ptr(out)))
     return out
 
 
 def field_from_bytes(field, b):
     """FromBytes for field elements; "Out of range" (field.rs:100) raises ValueError."""
-    L = _FIELD_LIMBS[field]
-    bb = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, L * 8)
+    L = _field_limbs(field)
+    bb = _u8(b, -1, L * 8)
     out = np.empty((bb.shape[0], L), dtype=np.uint64)
-    rc = _lib.load().plk_field_from_bytes(field, _ptr(bb), bb.shape[0], _ptr(out))
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        raise ValueError(_lib.load().plk_last_error().decode())
-    _lib.check(rc)
+    _call(_lib.load().plk_field_from_bytes(field, _ptr(bb), bb.shape[0], _ptr(out)), refusal=True)
     return out
 
 
 def point_to_bytes(curve, xy, zero=None):
     """ToBytes for AffinePoint: (n, 1 + BYTES) uint8: mask = zero | (y odd) << 1, then x."""
-    L = _CURVE_LIMBS[curve]
-    p = np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2, L)
-    z = np.ascontiguousarray(zero, dtype=np.uint8) if zero is not None else None
-    out = np.empty((p.shape[0], 1 + L * 8), dtype=np.uint8)
-    _lib.check(_lib.load().plk_curve_point_to_bytes(curve, _ptr(p), _ptr(z) if z is not None else None, p.shape[0], _ptr(out)))
+    p = _points(curve, xy)
+    z = _u8(zero)
+    out = np.empty((p.shape[0], 1 + p.shape[2] * 8), dtype=np.uint8)
+    _call(_lib.load().plk_curve_point_to_bytes(curve, _ptr(p), _ptr(z), p.shape[0], _ptr(out)))
     return out
 
 
 def point_from_bytes(curve, b, with_status=False):
     """FromBytes for AffinePoint: ((n, 2, L), zero flags); an undecodable record raises ValueError unless with_status."""
-    L = _CURVE_LIMBS[curve]
-    bb = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, 1 + L * 8)
+    L = _curve_limbs(curve)
+    bb = _u8(b, -1, 1 + L * 8)
     n = bb.shape[0]
     out = np.empty((n, 2, L), dtype=np.uint64)
     oz = np.zeros(n, dtype=np.uint8)
@@ -926,26 +935,18 @@ def point_from_bytes(curve, b, with_status=False):
     rc = _lib.load().plk_curve_point_from_bytes(curve, _ptr(bb), n, _ptr(out), _ptr(oz), _ptr(st))
     if with_status and rc in (_lib.PLK_OK, _lib.PLK_ERR_INVALID_ARG):
         return out, oz, st
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        raise ValueError(_lib.load().plk_last_error().decode())
-    _lib.check(rc)
+    _call(rc, refusal=True)
     return out, oz
 
 
 # ---- Pedersen generators: the BLAKE3 hash to the curve (hash_to_curve.rs:13-76) ----
-def _no_point(rc):
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        raise ValueError(_lib.load().plk_last_error().decode())
-    _lib.check(rc)
-
-
 def blake_field(field, iters, seeds):
     """blake_field(iter, seed) per row: seeds (n, L) Montgomery limbs, iters a u8 per row (or one for all).  Returns (x (n, L), y_neg (n,))."""
     a = _elems(field, seeds)
-    it = np.ascontiguousarray(np.broadcast_to(np.asarray(iters, dtype=np.uint8), (a.shape[0],)))
+    it = _u8(np.broadcast_to(np.asarray(iters, dtype=np.uint8), (a.shape[0],)))
     x = np.empty_like(a)
     y_neg = np.zeros(a.shape[0], dtype=np.uint8)
-    _no_point(_lib.load().plk_blake_field(a.shape[0], field, _ptr(it), _ptr(a), _ptr(x), _ptr(y_neg)))
+    _call(_lib.load().plk_blake_field(a.shape[0], field, _ptr(it), _ptr(a), _ptr(x), _ptr(y_neg)), refusal=True)
     return x, y_neg
 
 
@@ -953,15 +954,15 @@ def blake_hash_base_field_to_curve(curve, seeds):
     """blake_hash_base_field_to_curve::<C>(seed) per row of seeds ((n, L) Montgomery limbs of the base field): (n, 2, L) affine points."""
     a = _elems(CURVE_BASE_FIELD[curve], seeds)
     out = np.empty((a.shape[0], 2, a.shape[1]), dtype=np.uint64)
-    _no_point(_lib.load().plk_hash_field_to_curve(a.shape[0], curve, _ptr(a), _ptr(out)))
+    _call(_lib.load().plk_hash_field_to_curve(a.shape[0], curve, _ptr(a), _ptr(out)), refusal=True)
     return out
 
 
 def blake_hash_usize_to_curve(curve, seed, count=None):
     """blake_hash_usize_to_curve::<C>(seed): (2, L); with count, the points of seed .. seed + count - 1: (count, 2, L)."""
     n = 1 if count is None else int(count)
-    out = np.empty((n, 2, _CURVE_LIMBS[curve]), dtype=np.uint64)
-    _no_point(_lib.load().plk_hash_to_curve(n, curve, int(seed), _ptr(out)))
+    out = np.empty((n, 2, _curve_limbs(curve)), dtype=np.uint64)
+    _call(_lib.load().plk_hash_to_curve(n, curve, int(seed), _ptr(out)), refusal=True)
     return out[0] if count is None else out
 
 
@@ -975,23 +976,17 @@ def pedersen_generators(curve, degree):
 RESCUE_SPONGE_WIDTH, RESCUE_SPONGE_RATE = 4, 3
 
 
-def _refused(rc):
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        raise ValueError(_lib.load().plk_last_error().decode())
-    _lib.check(rc)
-
-
 def rescue_rounds(width, security_bits):
     """recommended_rounds (rescue.rs:123-125)."""
     r = ctypes.c_size_t(0)
-    _refused(_lib.load().plk_rescue_rounds(int(width), int(security_bits), ctypes.byref(r)))
+    _call(_lib.load().plk_rescue_rounds(int(width), int(security_bits), ctypes.byref(r)), refusal=True)
     return int(r.value)
 
 
 def rescue_mds(field, width=RESCUE_SPONGE_WIDTH):
     """mds_matrix::<F>(width) (mds.rs:56-77): (width, width, L) Montgomery limbs."""
-    out = np.empty((width, width, _FIELD_LIMBS.get(field, 4)), dtype=np.uint64)
-    _refused(_lib.load().plk_rescue_mds(int(width), field, _ptr(out)))
+    out = np.empty((width, width, _field_limbs(field, strict=False)), dtype=np.uint64)
+    _call(_lib.load().plk_rescue_mds(int(width), field, _ptr(out)), refusal=True)
     return out
 
 
@@ -1002,14 +997,14 @@ class RescueContext:
     ChaCha8Rng::seed_from_u64(1337), which is not restated here)."""
 
     def __init__(self, field, constants, width=RESCUE_SPONGE_WIDTH, rounds=None):
-        L = _FIELD_LIMBS.get(field, 4)
-        c = np.ascontiguousarray(constants, dtype=np.uint64)
+        L = _field_limbs(field, strict=False)
+        c = _u64(constants)
         if rounds is None:
             rounds = c.size // (2 * width * L) if width else 0
         assert c.size == rounds * 2 * width * L, "constants: rounds x 2 x width elements"
         self.field, self.width, self.rounds = field, int(width), int(rounds)
         self._ctx = ctypes.c_void_p()
-        _refused(_lib.load().plk_rescue_create(self.width, field, self.rounds, _ptr(c), ctypes.byref(self._ctx)))
+        _call(_lib.load().plk_rescue_create(self.width, field, self.rounds, _ptr(c), ctypes.byref(self._ctx)), refusal=True)
 
     @property
     def handle(self):
@@ -1018,7 +1013,7 @@ class RescueContext:
 
     def free(self):
         if self._ctx is not None and self._ctx.value:
-            _lib.check(_lib.load().plk_rescue_free(self._ctx))
+            _call(_lib.load().plk_rescue_free(self._ctx))
         self._ctx = None
 
     def __enter__(self):
@@ -1036,23 +1031,23 @@ class RescueContext:
 
 def rescue_permutation(ctx, states):
     """rescue_permutation (rescue.rs:70-88) per state: (n, 4, L) or (4, L) Montgomery limbs -> the same shape."""
-    a = np.ascontiguousarray(states, dtype=np.uint64)
-    L = _FIELD_LIMBS[ctx.field]
+    a = _u64(states)
+    L = _field_limbs(ctx.field)
     assert a.shape[-2:] == (ctx.width, L)
     out = np.empty_like(a)
-    _refused(_lib.load().plk_rescue_permutation(a.size // (ctx.width * L), ctx.handle, _ptr(a), _ptr(out)))
+    _call(_lib.load().plk_rescue_permutation(a.size // (ctx.width * L), ctx.handle, _ptr(a), _ptr(out)), refusal=True)
     return out
 
 
 def rescue_sponge(ctx, inputs, num_outputs):
     """rescue_sponge (rescue.rs:40-68) per row: inputs (n, n_inputs, L) or (n_inputs, L) -> (n, num_outputs, L) or (num_outputs, L)."""
-    L = _FIELD_LIMBS[ctx.field]
-    a = np.ascontiguousarray(inputs, dtype=np.uint64)
+    L = _field_limbs(ctx.field)
+    a = _u64(inputs)
     single = a.ndim == 2
     a = a.reshape((1,) + a.shape) if single else a
     assert a.ndim == 3 and a.shape[2] == L
     out = np.empty((a.shape[0], int(num_outputs), L), dtype=np.uint64)
-    _refused(_lib.load().plk_rescue_sponge(a.shape[0], ctx.handle, a.shape[1], _ptr(a), int(num_outputs), _ptr(out)))
+    _call(_lib.load().plk_rescue_sponge(a.shape[0], ctx.handle, a.shape[1], _ptr(a), int(num_outputs), _ptr(out)), refusal=True)
     return out[0] if single else out
 
 
@@ -1060,19 +1055,19 @@ def rescue_sponge(ctx, inputs, num_outputs):
 def hash_base_field_to_curve(ctx, curve, seeds):
     """hash_base_field_to_curve::<C>(seed, security_bits) per row of seeds ((n, L) or (L,) Montgomery limbs of the base field), the
     context's rounds standing for security_bits: (n, 2, L) or (2, L) affine points."""
-    a = np.ascontiguousarray(seeds, dtype=np.uint64)
+    a = _u64(seeds)
     single = a.ndim == 1
     a = _elems(CURVE_BASE_FIELD[curve], a.reshape(1, -1) if single else a)
     out = np.empty((a.shape[0], 2, a.shape[1]), dtype=np.uint64)
-    _refused(_lib.load().plk_rescue_hash_field_to_curve(a.shape[0], ctx.handle, curve, _ptr(a), _ptr(out)))
+    _call(_lib.load().plk_rescue_hash_field_to_curve(a.shape[0], ctx.handle, curve, _ptr(a), _ptr(out)), refusal=True)
     return out[0] if single else out
 
 
 def hash_usize_to_curve(ctx, curve, seed, count=None):
     """hash_usize_to_curve::<C>(seed, security_bits): (2, L); with count, the points of seed .. seed + count - 1: (count, 2, L)."""
     n = 1 if count is None else int(count)
-    out = np.empty((n, 2, _CURVE_LIMBS.get(curve, 4)), dtype=np.uint64)
-    _refused(_lib.load().plk_rescue_hash_to_curve(n, ctx.handle, curve, int(seed), _ptr(out)))
+    out = np.empty((n, 2, _curve_limbs(curve, strict=False)), dtype=np.uint64)
+    _call(_lib.load().plk_rescue_hash_to_curve(n, ctx.handle, curve, int(seed), _ptr(out)), refusal=True)
     return out[0] if count is None else out
 
 
@@ -1098,9 +1093,9 @@ def rescue_hash_n_to_3(ctx, inputs):  # rescue.rs:35-38
 
 def kth_root(field, x, k):
     """Field::kth_root_u32(k) (field.rs:340-375) per element of x ((n, L) Montgomery limbs); ValueError where the reference panics."""
-    a = np.ascontiguousarray(x, dtype=np.uint64)
+    a = _u64(x)
     out = np.empty_like(a)
-    _refused(_lib.load().plk_field_kth_root(a.size // _FIELD_LIMBS.get(field, 4), field, int(k), _ptr(a), _ptr(out)))
+    _call(_lib.load().plk_field_kth_root(a.size // _field_limbs(field, strict=False), field, int(k), _ptr(a), _ptr(out)), refusal=True)
     return out
 
 
@@ -1115,7 +1110,7 @@ class Challenger:
 
     def __init__(self, ctx):
         self.ctx = ctx
-        self.sponge_state = np.zeros((RESCUE_SPONGE_WIDTH, _FIELD_LIMBS[ctx.field]), dtype=np.uint64)
+        self.sponge_state = np.zeros((RESCUE_SPONGE_WIDTH, _field_limbs(ctx.field)), dtype=np.uint64)
         self.input_buffer = []
         self.output_buffer = []
 
@@ -1128,7 +1123,7 @@ class Challenger:
 
     def observe_element(self, element):
         self.output_buffer = []
-        self.input_buffer.append(np.array(element, dtype=np.uint64).reshape(_FIELD_LIMBS[self.ctx.field]))
+        self.input_buffer.append(np.array(element, dtype=np.uint64).reshape(_field_limbs(self.ctx.field)))
 
     def observe_elements(self, elements):
         for e in elements:
@@ -1171,44 +1166,41 @@ class Challenger:
 # ---- a point times a scalar of its own, the Halo endomorphism and the group side of the verifier ----
 # (curve_multiplication.rs:5-85, plonk_util.rs:50-110 / 329-339, halo.rs:157-223, verifier.rs:173-186)
 def _scalar_mul_args(curve, scalars, points, zero):
-    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
-    p = _points(curve, points)
-    z = None if zero is None else np.ascontiguousarray(zero, dtype=np.uint8).reshape(-1)
+    s, p, z = _scalars(scalars), _points(curve, points), _u8(zero, -1)
     assert z is None or z.shape[0] == p.shape[0]
     count = max(s.shape[0], p.shape[0])
-    return s, p, z, count, np.zeros((count, 2, _CURVE_LIMBS[curve]), dtype=np.uint64), np.zeros(count, dtype=np.uint8)
+    return s, p, z, count, np.zeros((count, 2, p.shape[2]), dtype=np.uint64), np.zeros(count, dtype=np.uint8)
 
 
 def curve_scalar_mul(curve, scalars, points, zero=None):
     """CurveScalar * ProjectivePoint per element: out_i = [s_i] P_i.  scalars (n, 4) or (4,) Montgomery limbs in the curve's scalar
     field, points (n, 2, L) or (2, L) affine; a single scalar or a single point is broadcast.  Returns (points (n, 2, L), zero flags)."""
     s, p, z, count, out, oz = _scalar_mul_args(curve, scalars, points, zero)
-    _refused(_lib.load().plk_curve_scalar_mul(count, curve, s.shape[0], _ptr(s), p.shape[0], _ptr(p), _ptr(z) if z is not None else None,
-                                              _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_curve_scalar_mul(count, curve, s.shape[0], _ptr(s), p.shape[0], _ptr(p), _ptr(z), _ptr(out), _ptr(oz)), refusal=True)
     return out, oz
 
 
 def halo_n(curve, scalars, security_bits=128):
     """halo_n (plonk_util.rs:50-75) of to_canonical_bool_vec()[..security_bits] per scalar: (n, 4) Montgomery limbs, scalar field."""
-    s = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    s = _scalars(scalars)
     out = np.empty_like(s)
-    _refused(_lib.load().plk_halo_n(s.shape[0], curve, int(security_bits), _ptr(s), _ptr(out)))
+    _call(_lib.load().plk_halo_n(s.shape[0], curve, int(security_bits), _ptr(s), _ptr(out)), refusal=True)
     return out
 
 
 def halo_n_mul(curve, scalars, points, zero=None, security_bits=128):
     """halo_n_mul (plonk_util.rs:79-110) per element: [n(s_i)] P_i by Algorithm 1; shapes and broadcast as curve_scalar_mul."""
     s, p, z, count, out, oz = _scalar_mul_args(curve, scalars, points, zero)
-    _refused(_lib.load().plk_halo_n_mul(count, curve, int(security_bits), s.shape[0], _ptr(s), p.shape[0], _ptr(p),
-                                        _ptr(z) if z is not None else None, _ptr(out), _ptr(oz)))
+    _call(_lib.load().plk_halo_n_mul(count, curve, int(security_bits), s.shape[0], _ptr(s), p.shape[0], _ptr(p), _ptr(z), _ptr(out), _ptr(oz)),
+          refusal=True)
     return out, oz
 
 
 def halo_g(field, x, us):
     """halo_g (plonk_util.rs:329-339): g(x, us) = prod over us REVERSED of (u_i x^(2^j) + u_i^-1).  log n products: host-driven."""
-    u = np.ascontiguousarray(us, dtype=np.uint64).reshape(-1, 4)
+    u = _scalars(us)
     product = powers(field, x, 1)[0:1]  # ONE
-    x_power = np.ascontiguousarray(x, dtype=np.uint64).reshape(1, 4)
+    x_power = _u64(x, 1, 4)
     for i in range(u.shape[0] - 1, -1, -1):
         u_i = u[i:i + 1]
         term = field_op(field, "add", field_op(field, "mul", u_i, x_power), field_op(field, "inverse", u_i))
@@ -1228,6 +1220,11 @@ def _point_sum(curve, pts):
     return curve_sum_affine(curve, np.stack([p[0] for p in pts]), np.array([p[1] for p in pts], dtype=np.uint8))
 
 
+def _blinded(sf, a, c, d):
+    """a c + d in the scalar field: the z of a Schnorr proof"""
+    return field_op(sf, "add", field_op(sf, "mul", _u64(a, 1, 4), c), _u64(d, 1, 4))[0]
+
+
 def schnorr_protocol(curve, halo_a, halo_b, halo_g, randomness, u_prime, pedersen_h, d, s, challenge):
     """schnorr_protocol (halo.rs:157-182) with the nonces d, s and the challenge as arguments: R = [d](G + [b] U') + [s] H,
     z1 = a c + d, z2 = randomness c + s.  Returns ((R limbs, zero flag), z1, z2)."""
@@ -1235,13 +1232,10 @@ def schnorr_protocol(curve, halo_a, halo_b, halo_g, randomness, u_prime, pederse
     g, up, h = _point(curve, halo_g), _point(curve, u_prime), _point(curve, pedersen_h)
     bu, buz = curve_scalar_mul(curve, halo_b, up[0], [up[1]])
     gu = _point_sum(curve, [g, (bu[0], int(buz[0]))])
-    m, mz = curve_scalar_mul(curve, np.stack([np.asarray(d, dtype=np.uint64).reshape(4), np.asarray(s, dtype=np.uint64).reshape(4)]),
-                             np.stack([gu[0], h[0]]), [gu[1], h[1]])
+    m, mz = curve_scalar_mul(curve, np.stack([_scalar(d), _scalar(s)]), np.stack([gu[0], h[0]]), [gu[1], h[1]])
     r = _point_sum(curve, [(m[0], int(mz[0])), (m[1], int(mz[1]))])
-    c = np.asarray(challenge, dtype=np.uint64).reshape(1, 4)
-    z1 = field_op(sf, "add", field_op(sf, "mul", np.asarray(halo_a, dtype=np.uint64).reshape(1, 4), c), np.asarray(d, dtype=np.uint64).reshape(1, 4))[0]
-    z2 = field_op(sf, "add", field_op(sf, "mul", np.asarray(randomness, dtype=np.uint64).reshape(1, 4), c), np.asarray(s, dtype=np.uint64).reshape(1, 4))[0]
-    return r, z1, z2
+    c = _u64(challenge, 1, 4)
+    return r, _blinded(sf, halo_a, c, d), _blinded(sf, randomness, c, s)
 
 
 def verify_ipa(curve, halo_l, halo_r, halo_g, commitment, value, halo_b, halo_us, u_prime, pedersen_h, schnorr_challenge, schnorr_proof):
@@ -1249,26 +1243,25 @@ def verify_ipa(curve, halo_l, halo_r, halo_g, commitment, value, halo_b, halo_us
     (limbs, zero flag); scalars (4,) Montgomery limbs; schnorr_proof = (R, z1, z2).  P' = C + [value] U',
     Q = <u^2, L> + <u^-2, R> + P', and the check is [c] Q + R == [z1](G + [b] U') + [z2] H on unique affine points."""
     sf = int(_lib.load().plk_curve_scalar_field(curve))
-    us = np.ascontiguousarray(halo_us, dtype=np.uint64).reshape(-1, 4)
+    us = _scalars(halo_us)
     lr, lrz = [], []
     for side in (halo_l, halo_r):
         pts, flags = side if isinstance(side, tuple) else (side, None)
         pts = _points(curve, pts)
         assert pts.shape[0] == us.shape[0], "one L_j and one R_j per challenge"
         lr.append(pts)
-        lrz.append(np.zeros(pts.shape[0], dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8).reshape(-1))
+        lrz.append(np.zeros(pts.shape[0], dtype=np.uint8) if flags is None else _u8(flags, -1))
     g, com, up, h = _point(curve, halo_g), _point(curve, commitment), _point(curve, u_prime), _point(curve, pedersen_h)
     r, z1, z2 = schnorr_proof
     r = _point(curve, r)
-    one = lambda v: np.asarray(v, dtype=np.uint64).reshape(4)
     # [value] U' and [b] U': one call, two scalars over the one point
-    t, tz = curve_scalar_mul(curve, np.stack([one(value), one(halo_b)]), up[0], [up[1]])
+    t, tz = curve_scalar_mul(curve, np.stack([_scalar(value), _scalar(halo_b)]), up[0], [up[1]])
     p_prime = _point_sum(curve, [com, (t[0], int(tz[0]))])
     scalars = np.concatenate([field_op(sf, "square", us), field_op(sf, "square", field_op(sf, "inverse", us))])
     q = msm_parallel(curve, scalars, np.concatenate(lr), 8, zero=np.concatenate(lrz))
     q = _point_sum(curve, [q, p_prime])
     gu = _point_sum(curve, [g, (t[1], int(tz[1]))])
-    m, mz = curve_scalar_mul(curve, np.stack([one(schnorr_challenge), one(z1), one(z2)]), np.stack([q[0], gu[0], h[0]]), [q[1], gu[1], h[1]])
+    m, mz = curve_scalar_mul(curve, np.stack([_scalar(schnorr_challenge), _scalar(z1), _scalar(z2)]), np.stack([q[0], gu[0], h[0]]), [q[1], gu[1], h[1]])
     lhs = _point_sum(curve, [(m[0], int(mz[0])), r])
     rhs = _point_sum(curve, [(m[1], int(mz[1])), (m[2], int(mz[2]))])
     return lhs[1] == rhs[1] and bool(np.array_equal(lhs[0], rhs[0]))

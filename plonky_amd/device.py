@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import api as _api, lib as _lib
-from .api import _CURVE_LIMBS, _FIELD_LIMBS, MsmPrecomputation, _ptr as _hp, _u64, log2_strict
+from .api import _CURVE_LIMBS, _FIELD_LIMBS, MsmPrecomputation, _call, _ptr as _hp, _u64, log2_strict
 
 
 # ---- the marshalling layer: every wrapper below is a check, _out_tensor and one call ----
@@ -573,7 +573,7 @@ class HaloArgument:
             inside = u_prime_scalar is not None and h_index is not None and u_index is not None
             xs = _u64(u_prime_scalar, 4) if inside else None
             _lib.check(_lib.load().plk_halo_begin_tabled_dev(*vectors, tables._ctx, _hp(h), _hp(u), h_index if inside else NO, u_index if inside else NO,
-                                                             _hp(xs) if inside else None, freeze_log, lead_rounds, _stream(), ctypes.byref(ctx)))
+                                                             _hp(xs), freeze_log, lead_rounds, _stream(), ctypes.byref(ctx)))
         else:
             _lib.check(_lib.load().plk_halo_begin_dev(*vectors, _hp(h), _hp(u), freeze_log, _stream(), ctypes.byref(ctx)))
         self._ctx = ctx
@@ -639,19 +639,13 @@ def rescue_sponge_dev(ctx, inputs, num_outputs, out=None):
     return out
 
 
-def _rescue_h2c_call(rc):
-    if rc == _lib.PLK_ERR_INVALID_ARG:
-        raise ValueError(_lib.load().plk_last_error().decode())
-    _lib.check(rc)
-
-
 def rescue_hash_to_curve_dev(ctx, curve, count, seed_start=0, out=None, device="cuda"):
     """hash_usize_to_curve (hash_to_curve.rs:8-11, 78-104) of the integers seed_start .. seed_start + count - 1 on the device; ctx: an
     api.RescueContext over the curve's base field, its rounds standing for security_bits.  (count, 2, L) int64 tensor that
     msm_precompute_dev takes as it is."""
     out = _out_tensor(out, (count, 2, _CURVE_LIMBS[curve]), device)
     assert out.is_cuda  # a fresh one too: `device` is the caller's word
-    _rescue_h2c_call(_lib.load().plk_rescue_hash_to_curve_dev(count, ctx.handle, curve, int(seed_start), _dp(out), _stream()))
+    _call(_lib.load().plk_rescue_hash_to_curve_dev(count, ctx.handle, curve, int(seed_start), _dp(out), _stream()), refusal=True)
     return out
 
 
@@ -661,7 +655,7 @@ def rescue_hash_field_to_curve_dev(ctx, curve, seeds, out=None):
     _check(seeds, shape=(None, L))
     count = seeds.shape[0]
     out = _out_tensor(out, (count, 2, L), seeds.device)
-    _rescue_h2c_call(_lib.load().plk_rescue_hash_field_to_curve_dev(count, ctx.handle, curve, _dp(seeds), _dp(out), _stream()))
+    _call(_lib.load().plk_rescue_hash_field_to_curve_dev(count, ctx.handle, curve, _dp(seeds), _dp(out), _stream()), refusal=True)
     return out
 
 

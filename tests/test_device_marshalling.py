@@ -13,10 +13,9 @@ import pytest
 import torch
 
 from plonky_amd import device
+from tests.abi_recorder import ANYPTR, H, NULL, OUT, P, PA, REF, _Recorder, call, refused
 
 STREAM, CTX, TABLES, HANDLE = "stream", "ctx", "tables-ctx", "rescue-handle"
-NULL = ("ptr", None)
-ANYPTR = ("anyptr",)
 NO = ctypes.c_size_t(-1).value
 FIELDS = ((0, 4), (3, 6))  # (field id, limbs): TweedledeeBase, Bls12377Base
 CURVES = ((0, 4), (2, 6))  # (curve id, limbs): Tweedledee, Bls12377
@@ -45,96 +44,12 @@ def limbs(*shape, seed=1):
     return (np.arange(int(np.prod(shape)), dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(seed)).reshape(shape)
 
 
-def P(t):
-    """a pointer to this tensor's (or array's) memory"""
-    return ("ptr", (t.ctypes.data if isinstance(t, np.ndarray) else t.data_ptr()) or None)
-
-
-def H(a, dtype=np.uint64):
-    """a pointer to host memory with this content"""
-    return ("host", np.ascontiguousarray(a, dtype=dtype).tobytes())
-
-
-def PA(ts):
-    """a ctypes array of pointers"""
-    return ("ptrs", [None if t is None else t.data_ptr() for t in ts])
-
-
-def REF(ctype):
-    """byref() of an out-parameter of this type"""
-    return ("ref", ctype)
-
-
-def OUT(i=None):
-    """a pointer to what the wrapper returns (its i-th result)"""
-    return ("out", i)
-
-
-def _snap(arg, want):
-    kind = want[0] if isinstance(want, tuple) and want else None
-    if kind in ("ptr", "out", "anyptr", "host"):
-        if kind == "host" and not want[1] and (arg is None or isinstance(arg, ctypes.c_void_p)):
-            return want  # nothing to read: any pointer will do
-        if arg is None or (isinstance(arg, ctypes.c_void_p) and arg.value is None):
-            return NULL
-        if not isinstance(arg, ctypes.c_void_p):
-            return ("not a pointer", arg)
-        if kind == "host":
-            return ("host", ctypes.string_at(arg, len(want[1])))
-        return ANYPTR if kind == "anyptr" else ("ptr", arg.value)
-    if kind == "ptrs":
-        return ("ptrs", list(arg))
-    if kind == "ref":
-        return ("ref", type(arg._obj))
-    return arg
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls, self.want = [], []
-
-    def __getattr__(self, name):
-        if not name.startswith("plk_"):
-            raise AttributeError(name)
-
-        def entry(*args):
-            want = self.want[len(self.calls)][1:] if len(self.calls) < len(self.want) else ()
-            self.calls.append((name,) + tuple(_snap(a, w) for a, w in itertools.zip_longest(args, want)))
-            return 0
-
-        return entry
-
-
 @pytest.fixture
 def rec(monkeypatch):
     r = _Recorder()
     monkeypatch.setattr(device._lib, "load", lambda: r)
     monkeypatch.setattr(device, "_stream", lambda: STREAM)
     return r
-
-
-def call(rec, want, fn, *args, **kwargs):
-    """Run the wrapper, which must make exactly the C call(s) `want`; returns the wrapper's result."""
-    wants = want if isinstance(want, list) else [want]
-    rec.calls, rec.want = [], wants
-    result = fn(*args, **kwargs)
-
-    def resolve(w):
-        if isinstance(w, tuple) and w and w[0] == "out":
-            r = result if w[1] is None else result[w[1]]
-            return NULL if r is None else P(r)
-        return w
-
-    assert rec.calls == [tuple(resolve(w) for w in one) for one in wants]
-    rec.calls, rec.want = [], []
-    return result
-
-
-def refused(rec, fn, *args, **kwargs):
-    rec.calls, rec.want = [], []
-    with pytest.raises(AssertionError):
-        fn(*args, **kwargs)
-    assert rec.calls == []
 
 
 def bad_tensors(*shape, dtype=torch.int64, wrong_dtype=torch.int32):
