@@ -712,8 +712,10 @@ int plk_msm_get_timings(plk_msm_ctx* ctx, double* sum_ms, unsigned* calls);
  * reference's binary Euclid (bigint_inverse.rs:6-55), 9 inverse by division steps (the one the kernels
  * use), 10 the same in its data-dependent form, 11 that form with ONE active lane per wave (the normalisation at the end of an MSM);
  * 12 / 13: the shared-reduction arithmetic of the kernels on fixed limb patterns derived from a and b (sums of two products through one
- * Montgomery reduction at the edge of their column bound; the column accumulators of the quotient numerator) - parity tests only.
- * b ignored for unary. */
+ * Montgomery reduction at the edge of their column bound; the column accumulators of the quotient numerator) - parity tests only;
+ * 14 Field::square_root(a) (field.rs:440-472) by the reference's squarings, as the point decompression calls it, 15 the same root from
+ * the table of powers of the 2-adic root, as the hashes to the curve call it (the table is built per call); a non-residue gives all
+ * words 0xFFFFFFFF, which is no reduced element of any field.  b ignored for unary. */
 int plk_field_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
 /* Element-wise point arithmetic of the MSM kernels (ecz.cuh, ecz_coop.cuh) on host arrays of `count` <= 2048 elements - parity tests only
  * (tests/test_gpu_group_law.py compares every result with big integers).  An operand is an affine point (2L limbs, Montgomery; identity

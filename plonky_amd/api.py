@@ -527,11 +527,13 @@ def affine_multisummation_best(curve, summations, zeros=None):
 
 FIELD_OPS = {"add": 0, "sub": 1, "mul": 2, "neg": 3, "square": 4, "inverse": 5, "to_canonical": 6, "from_canonical": 7,
              "inverse_euclid": 8, "inverse_divsteps": 9, "inverse_divsteps_var": 10, "inverse_divsteps_one_lane": 11,
-             "mul_add2_edge": 12, "wide_sum": 13}
+             "mul_add2_edge": 12, "wide_sum": 13, "sqrt": 14, "sqrt_tabled": 15}
+FIELD_OP_NO_ROOT = 0xFFFFFFFFFFFFFFFF  # every limb of what "sqrt" / "sqrt_tabled" write for a non-residue: no reduced element of any field
 
 
 def field_op(field, op, a, b=None):
-    """Element-wise device field arithmetic (parity tests of the HIP field code)."""
+    """Element-wise device field arithmetic (parity tests of the HIP field code).  "sqrt" is Field::square_root by the reference's
+    squarings (fe_sqrt), "sqrt_tabled" the same root from the table of powers the hashes to the curve use (fe_sqrt_tabled)."""
     a = _elems(field, a)
     out = np.empty_like(a)
     bb = a if b is None else _elems(field, b)

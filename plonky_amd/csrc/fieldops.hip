@@ -3,12 +3,16 @@
 // tests can run the HIP field arithmetic itself against the oracle on the edge-value inputs.
 #include "common.h"
 #include "ec.cuh"
+#include "fe_sqrt.cuh"
 #include "fp.cuh"
 #include "fz.cuh"
 
 namespace plk {
 
-template <class P> __global__ void k_field_op(int op, const uint4* a, const uint4* b, uint4* out, size_t count) {
+// ops that read the second operand
+static inline __host__ __device__ bool field_op_is_binary(int op) { return op <= 2 || op == 12 || op == 13; }
+
+template <class P> __global__ void k_field_op(int op, const uint4* a, const uint4* b, uint4* out, size_t count, const uint4* root_tab) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (op == 11) {  // the one-lane inversion: ONE active lane per wave, element = wave index
         if (threadIdx.x & 63) return;
@@ -17,7 +21,7 @@ template <class P> __global__ void k_field_op(int op, const uint4* a, const uint
     if (i >= count) return;
     constexpr int W = P::NL / 4;
     Fe<P> x = fe_load<P>(a + i * W), y = fe_zero<P>(), r;
-    if (op <= 2 || op >= 12) y = fe_load<P>(b + i * W);
+    if (field_op_is_binary(op)) y = fe_load<P>(b + i * W);
     switch (op) {
         case 0: r = fe_add<P>(x, y); break;
         case 1: r = fe_sub<P>(x, y); break;
@@ -58,6 +62,12 @@ template <class P> __global__ void k_field_op(int op, const uint4* a, const uint
             fz_wide_add<P>(w, xz);
             r = fz_to_fe_canonical<P>(fz_mul<P>(fz_wide_reduce<P>(w), fz_one_rprime<P>()));
         } break;
+        case 14:    // Field::square_root by the reference's squarings (what serial.hip calls)
+        case 15: {  // the same root with the table of k_h2c_root_table in place of the squarings (what the two hashes to the curve call)
+            const bool square = op == 14 ? fe_sqrt<P>(x, r) : fe_sqrt_tabled<P>(x, r, root_tab);
+            if (!square)  // None: all words 0xFFFFFFFF, which is no reduced element of any field
+                for (int k = 0; k < P::NL; ++k) r.v[k] = 0xFFFFFFFFu;
+        } break;
         default: r = fe_inv_safegcd<P>(x); break;      // what the kernels use
     }
     fe_store<P>(out + i * W, r);
@@ -65,15 +75,20 @@ template <class P> __global__ void k_field_op(int op, const uint4* a, const uint
 
 template <class P> static int field_op_t(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
     const size_t bytes = count * P::NL * 4;
-    DevBuf da, db, dout;
+    DevBuf da, db, dout, dtab;
     PLK_TRY(da.alloc(bytes));
     PLK_TRY(db.alloc(bytes));
     PLK_TRY(dout.alloc(bytes));
     PLK_HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-    if (op <= 2 || op >= 12) PLK_HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
+    if (field_op_is_binary(op)) PLK_HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
     if (count) {
+        if (op == 15) {  // the table of the tabled root, built as the hashes to the curve build theirs
+            PLK_TRY(dtab.alloc((size_t)P::TWO_ADICITY * P::NL * 4));
+            k_h2c_root_table<P><<<1, 1>>>((uint4*)dtab.p);
+            PLK_HIP_TRY(hipGetLastError());
+        }
         const size_t lanes = op == 11 ? count * 64 : count;
-        k_field_op<P><<<(unsigned)((lanes + 127) / 128), 128>>>(op, (const uint4*)da.p, (const uint4*)db.p, (uint4*)dout.p, count);
+        k_field_op<P><<<(unsigned)((lanes + 127) / 128), 128>>>(op, (const uint4*)da.p, (const uint4*)db.p, (uint4*)dout.p, count, (const uint4*)dtab.p);
         PLK_HIP_TRY(hipGetLastError());
     }
     PLK_HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
@@ -297,8 +312,8 @@ int field_fold_slices_dev_impl(int field, const void* d_lo, const void* d_hi, co
 }
 
 int field_op_impl(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
-    if (op < 0 || op > 13) return set_error(PLK_ERR_INVALID_ARG, "bad field op %d", op);
-    if (!a || !out || ((op <= 2 || op >= 12) && !b)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
+    if (op < 0 || op > 15) return set_error(PLK_ERR_INVALID_ARG, "bad field op %d", op);
+    if (!a || !out || (field_op_is_binary(op) && !b)) return set_error(PLK_ERR_INVALID_ARG, "null pointer");
     PLK_TRY(ensure_device());
     return or_bad_field(with_field(field, [&](auto t) { return field_op_t<tag_t<decltype(t)>>(op, a, b, out, count); }), field);
 }

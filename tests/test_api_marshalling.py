@@ -390,10 +390,11 @@ def test_batch_to_affine(rec):
 
 
 OPS = ("add", "sub", "mul", "neg", "square", "inverse", "to_canonical", "from_canonical", "inverse_euclid", "inverse_divsteps", "inverse_divsteps_var",
-       "inverse_divsteps_one_lane", "mul_add2_edge", "wide_sum")
+       "inverse_divsteps_one_lane", "mul_add2_edge", "wide_sum", "sqrt", "sqrt_tabled")
 
 
 def test_field_op(rec):
+    assert api.FIELD_OPS == {op: code for code, op in enumerate(OPS)}
     for (field, L), (code, op) in itertools.product(FIELDS, enumerate(OPS)):
         a, b = limbs(3, L), limbs(3, L, seed=7)
         assert is_u64(call(rec, ("plk_field_op", field, code, H(a), H(b), OUT(), 3), api.field_op, field, op, a.tolist(), b.reshape(-1)), 3, L)
