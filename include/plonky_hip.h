@@ -749,7 +749,8 @@ int plk_bench_ceilings(double* out, unsigned n_out);
  * (tests/test_gpu_parity.py pins them to the vector of curve_msm.rs:186-216). */
 int plk_msm_debug_digits(int curve, unsigned window_bits, size_t n, const uint64_t* scalars, int32_t* digits, unsigned* n_digits);
 /* Synthetic generators B_i = G0 + (first + i) * D, i < n, affine, written to DEVICE memory
- * (n * 2L limbs).  g0_xy / d_xy are host pointers (2L limbs each). */
+ * (n * 2L limbs).  g0_xy / d_xy are host pointers (2L limbs each).  The entry has no identity flag: the caller must avoid a G0, D
+ * and range with G0 + (first + i) D = the identity (D = -G0 at first + i = 1, for one), for which the words written are zero. */
 int plk_curve_gen_bases_dev(int curve, size_t n, uint64_t first, const uint64_t* g0_xy, const uint64_t* d_xy, void* d_out_xy, void* stream);
 
 #ifdef __cplusplus

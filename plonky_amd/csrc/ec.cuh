@@ -125,7 +125,8 @@ template <class FP> __device__ __noinline__ Xyzz<FP> xyzz_dbl(const Xyzz<FP>& p)
 }
 
 // acc += (x2, y2), the affine operand is never the identity (EFD madd-2008-s + exceptional cases;
-// the P+A branches of curve_adds.rs:50-90)
+// the P+A branches of curve_adds.rs:50-90).  tests/test_gpu_xyzz_law.py drives the exceptional branches of this law (here and in
+// xyzz_add: identity, doubling, cancelling, y = 0) through k_sum_affine, k_combine_partials and k_gen_bases against big integers.
 template <class FP> PLK_DI void xyzz_madd(Xyzz<FP>& acc, const Fe<FP>& x2, const Fe<FP>& y2) {
     if (xyzz_is_identity<FP>(acc)) {
         acc = xyzz_from_affine<FP>(x2, y2);
