@@ -1,6 +1,6 @@
 // fe_sqrt_host_replay.cpp -- plonky_amd/csrc/fe_sqrt.cuh (fe_sqrt_with: the Tonelli-Shanks loop that the point decompression and the two
 // hashes to the curve run) compiled for the host and run as a program of its own: tests/test_fe_sqrt_host_replay.py builds it plain and
-// with -fsanitize=address,undefined and compares what it prints with tests/sqrt_cases.py.  Every input goes through the loop twice: with
+// under AddressSanitizer + UBSan and compares what it prints with tests/sqrt_cases.py.  Every input goes through the loop twice: with
 // SqrtRootBySquaring (fe_sqrt) and with a host table functor that indexes tab[m] = ROOT_2ADIC^(2^m) exactly as SqrtRootFromTable does
 // (fe_sqrt_tabled); the table is built by the loop of k_h2c_root_table.
 //
@@ -14,30 +14,9 @@
 
 #include "../plonky_amd/csrc/dispatch.cuh"
 #include "../plonky_amd/csrc/fe_sqrt.cuh"
+#include "replay_io.h"
 
 using namespace plk;
-
-static bool token(FILE* fh, std::string& s) {
-    char buf[256];
-    if (fscanf(fh, "%255s", buf) != 1) return false;
-    s = buf;
-    return true;
-}
-template <class P> static bool read_fe(FILE* fh, Fe<P>& v) {
-    std::string s;
-    if (!token(fh, s) || s.size() != (size_t)P::NL * 8) return false;
-    for (int k = 0; k < P::NL; ++k) v.v[k] = (uint32_t)strtoul(s.substr((size_t)(P::NL - 1 - k) * 8, 8).c_str(), nullptr, 16);
-    return true;
-}
-template <int NL> static std::string hex_words(const uint32_t (&w)[NL]) {
-    std::string s;
-    char buf[9];
-    for (int k = NL - 1; k >= 0; --k) {
-        snprintf(buf, sizeof(buf), "%08x", w[k]);
-        s += buf;
-    }
-    return s;
-}
 
 // SqrtRootFromTable on a host vector: the same index, checked against the table's length
 template <class P> struct HostRootFromTable {

@@ -1,5 +1,5 @@
 // hash_to_curve_host_replay.cpp -- plonky_amd/csrc/h2c_step.cuh (the BLAKE3 block and blake_field) compiled for the host and run as a
-// program of its own: tests/test_hash_to_curve_host_replay.py builds it plain and with -fsanitize=address,undefined and compares what
+// program of its own: tests/test_hash_to_curve_host_replay.py builds it plain and under AddressSanitizer + UBSan and compares what
 // it prints with tests/hash_to_curve_ref.py.
 //
 //   hash_to_curve_host_replay CASES
@@ -12,6 +12,7 @@
 
 #include "../plonky_amd/csrc/dispatch.cuh"
 #include "../plonky_amd/csrc/h2c_step.cuh"
+#include "replay_io.h"
 
 using namespace plk;
 
@@ -30,16 +31,6 @@ static void digest(const char* text, int first_byte) {
     for (size_t k = 0; k < len; ++k) m[k / 4] |= (uint32_t)(unsigned char)text[k] << (8 * (k % 4));
     h2c_blake3_block(m, (uint32_t)len, out);
     printf("%s\n", hex_bytes(out, first_byte, 32).c_str());
-}
-
-template <int NL> static std::string hex_value(const uint32_t (&w)[NL]) {  // a number, most significant digit first
-    std::string s;
-    char buf[9];
-    for (int k = NL - 1; k >= 0; --k) {
-        snprintf(buf, sizeof(buf), "%08x", w[k]);
-        s += buf;
-    }
-    return s;
 }
 
 int main(int argc, char** argv) {
@@ -67,7 +58,7 @@ int main(int argc, char** argv) {
             uint32_t seed[P::NL], x[P::NL] = {0}, y_neg = 0, j = 0;
             for (int k = 0; k < P::NL; ++k) seed[k] = (uint32_t)strtoul(sh.substr((size_t)(P::NL - 1 - k) * 8, 8).c_str(), nullptr, 16);
             const bool ok = h2c_blake_field<P>(seed, iter, x, y_neg, j);
-            printf("%d %s %u %d %s %u %u\n", field, sh.c_str(), iter, ok ? 1 : 0, hex_value(x).c_str(), y_neg, j);
+            printf("%d %s %u %d %s %u %u\n", field, sh.c_str(), iter, ok ? 1 : 0, hex_words(x).c_str(), y_neg, j);
             return 0;
         });
         if (m != 0) {

@@ -6,18 +6,9 @@
 #include <vector>
 #include "../plonky_amd/csrc/fp.cuh"
 #include "../plonky_amd/csrc/fz.cuh"
+#include "replay_io.h"
 using namespace plk;
-template <class P> Fe<P> to_rprime(const Fe<P>& v) { return fz_to_fe_canonical<P>(fz_mul<P>(fz_from_fe<P>(v), fz_const_r_to_rprime<P>())); }
 template <class P> Fe<P> fe_pow_u64(Fe<P> x, uint64_t e) { Fe<P> r = fe_one<P>(); while (e) { if (e & 1) r = fe_mul<P>(r, x); x = fe_sqr<P>(x); e >>= 1; } return r; }
-template <class P> Fe<P> rnd(int edge) {
-    Fe<P> r;
-    for (int i = 0; i < P::NL; ++i) r.v[i] = (uint32_t)rand() * 2654435761u ^ (uint32_t)rand();
-    r.v[P::NL - 1] &= 0x0fffffffu;
-    if (edge == 1) r = fe_zero<P>();
-    if (edge == 2) r = fe_neg<P>(fe_one<P>());
-    if (edge == 3) { r = fe_zero<P>(); r = fe_sub<P>(r, fe_from_canonical<P>(fe_one<P>())); r = fe_to_canonical<P>(fe_neg<P>(fe_one<P>())); }  // stored word p - 1
-    return r;
-}
 template <class P> int run() {
     const int LANES = 256, G = 6, ROWS = 4, T = 24; const size_t TILE = LANES * T;
     int bad = 0;

@@ -8,18 +8,8 @@
 #include "../plonky_amd/csrc/fp.cuh"
 #include "../plonky_amd/csrc/fz.cuh"
 #include "../plonky_amd/csrc/polydiv_step.cuh"
+#include "replay_io.h"
 using namespace plk;
-template <class P> Fe<P> to_rprime(const Fe<P>& v) { return fz_to_fe_canonical<P>(fz_mul<P>(fz_from_fe<P>(v), fz_const_r_to_rprime<P>())); }
-template <class P> Fe<P> rnd(int edge) {
-    Fe<P> r;
-    for (int i = 0; i < P::NL; ++i) r.v[i] = (uint32_t)rand() * 2654435761u ^ (uint32_t)rand();
-    r.v[P::NL - 1] &= 0x0fffffffu;
-    if (edge == 1) r = fe_zero<P>();                              // the stored word 0
-    if (edge == 2) r = fe_neg<P>(fe_one<P>());                    // the value p - 1
-    if (edge == 3) r = fe_to_canonical<P>(fe_neg<P>(fe_one<P>())); // the stored word p - 1
-    if (edge == 4) { r = fe_zero<P>(); r.v[0] = 1; }                // the stored word 1
-    return r;
-}
 template <class P> Fe<P> rnd_mixed() { return rnd<P>(rand() % 16 < 4 ? 1 + rand() % 4 : 0); }
 
 // one pass over a segment, as pdiv_run_segment does it on the kp lanes of a group

@@ -13,26 +13,17 @@
 #include "../plonky_amd/csrc/fp.cuh"
 #include "../plonky_amd/csrc/fz.cuh"
 #include "../plonky_amd/csrc/polyinv_step.cuh"
+#include "replay_io.h"
 using namespace plk;
 
-template <class P> Fe<P> to_rprime(const Fe<P>& v) { return fz_to_fe_canonical<P>(fz_mul<P>(fz_from_fe<P>(v), fz_const_r_to_rprime<P>())); }
-template <class P> Fe<P> read_word(FILE* f) {
-    char buf[80];
-    if (fscanf(f, "%79s", buf) != 1 || strlen(buf) != 64) exit(2);
+template <class P> Fe<P> read_word(FILE* f) {  // big-endian hex of the 256-bit stored word
     Fe<P> r;
-    for (int i = 0; i < 8; ++i) {  // big-endian hex of the 256-bit stored word
-        char part[9] = {0};
-        memcpy(part, buf + 8 * (7 - i), 8);
-        r.v[i] = (uint32_t)strtoul(part, nullptr, 16);
-    }
+    if (!read_fe<P>(f, r)) exit(2);
     return r;
 }
 template <class P> void print_words(const char* tag, const std::vector<Fe<P>>& v) {
     printf("%s", tag);
-    for (const auto& e : v) {
-        printf(" ");
-        for (int i = 7; i >= 0; --i) printf("%08x", e.v[i]);
-    }
+    for (const auto& e : v) printf(" %s", hex_words(e.v).c_str());
     printf("\n");
 }
 template <class P> using Vec = std::vector<Fe<P>>;

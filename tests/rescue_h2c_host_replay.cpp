@@ -1,6 +1,6 @@
 // rescue_h2c_host_replay.cpp -- plonky_amd/csrc/rescue_h2c_step.cuh (the seed formation, the y_neg bit, the curve half of a try and the
 // bounded loop over the tries: the code k_rescue_h2c_tries runs) compiled for the host and run as a program of its own:
-// tests/test_rescue_h2c_host_replay.py builds it plain and with -fsanitize=address,undefined and compares what it prints with
+// tests/test_rescue_h2c_host_replay.py builds it plain and under AddressSanitizer + UBSan and compares what it prints with
 // tests/rescue_h2c_ref.py.  The sponge is rescue_h2c_sponge_state (a whole state through rescue_permutation_step), the root fe_sqrt.
 //
 //   rescue_h2c_host_replay CASES
@@ -16,30 +16,9 @@
 
 #include "../plonky_amd/csrc/dispatch.cuh"
 #include "../plonky_amd/csrc/rescue_h2c_step.cuh"
+#include "replay_io.h"
 
 using namespace plk;
-
-static bool token(FILE* fh, std::string& s) {
-    char buf[256];
-    if (fscanf(fh, "%255s", buf) != 1) return false;
-    s = buf;
-    return true;
-}
-template <class P> static bool read_fe(FILE* fh, Fe<P>& v) {
-    std::string s;
-    if (!token(fh, s) || s.size() != (size_t)P::NL * 8) return false;
-    for (int k = 0; k < P::NL; ++k) v.v[k] = (uint32_t)strtoul(s.substr((size_t)(P::NL - 1 - k) * 8, 8).c_str(), nullptr, 16);
-    return true;
-}
-template <int NL> static std::string hex_words(const uint32_t (&w)[NL]) {
-    std::string s;
-    char buf[9];
-    for (int k = NL - 1; k >= 0; --k) {
-        snprintf(buf, sizeof(buf), "%08x", w[k]);
-        s += buf;
-    }
-    return s;
-}
 
 template <class P> static int seed_case(FILE* fh, int field) {
     std::string ns;

@@ -1,6 +1,6 @@
 // rescue_host_replay.cpp -- plonky_amd/csrc/rescue_step.cuh (the exponent of a k-th root, the Cauchy matrix, the windowed power chain,
 // the row sum and the round: the code the kernels of rescue.hip run) compiled for the host and run as a program of its own:
-// tests/test_rescue_host_replay.py builds it plain and with -fsanitize=address,undefined and compares what it prints with
+// tests/test_rescue_host_replay.py builds it plain and under AddressSanitizer + UBSan and compares what it prints with
 // tests/rescue_ref.py.
 //
 //   rescue_host_replay CASES
@@ -15,30 +15,9 @@
 
 #include "../plonky_amd/csrc/dispatch.cuh"
 #include "../plonky_amd/csrc/rescue_step.cuh"
+#include "replay_io.h"
 
 using namespace plk;
-
-static bool token(FILE* fh, std::string& s) {
-    char buf[256];
-    if (fscanf(fh, "%255s", buf) != 1) return false;
-    s = buf;
-    return true;
-}
-template <class P> static bool read_fe(FILE* fh, Fe<P>& v) {
-    std::string s;
-    if (!token(fh, s) || s.size() != (size_t)P::NL * 8) return false;
-    for (int k = 0; k < P::NL; ++k) v.v[k] = (uint32_t)strtoul(s.substr((size_t)(P::NL - 1 - k) * 8, 8).c_str(), nullptr, 16);
-    return true;
-}
-template <int NL> static std::string hex_words(const uint32_t (&w)[NL]) {
-    std::string s;
-    char buf[9];
-    for (int k = NL - 1; k >= 0; --k) {
-        snprintf(buf, sizeof(buf), "%08x", w[k]);
-        s += buf;
-    }
-    return s;
-}
 
 template <class P> static int matrix(int field) {
     printf("M %d %u", field, rescue_alpha<P>());

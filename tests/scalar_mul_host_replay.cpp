@@ -1,6 +1,6 @@
 // scalar_mul_host_replay.cpp -- plonky_amd/csrc/scalar_mul_step.cuh (the chunk decoding and n(s), the signed-digit recoding, the
 // split along the endomorphism and the addend selections: the code the kernels of scalar_mul.hip run) compiled for the host and run
-// as a program of its own: tests/test_scalar_mul_host_replay.py builds it plain and with -fsanitize=address,undefined and compares
+// as a program of its own: tests/test_scalar_mul_host_replay.py builds it plain and under AddressSanitizer + UBSan and compares
 // what it prints with tests/halo_endo_ref.py.
 //
 //   scalar_mul_host_replay CASES
@@ -19,30 +19,9 @@
 
 #include "../plonky_amd/csrc/ec.cuh"
 #include "../plonky_amd/csrc/scalar_mul_step.cuh"
+#include "replay_io.h"
 
 using namespace plk;
-
-static bool token(FILE* fh, std::string& s) {
-    char buf[256];
-    if (fscanf(fh, "%255s", buf) != 1) return false;
-    s = buf;
-    return true;
-}
-template <int NL> static bool read_words(FILE* fh, uint32_t (&v)[NL]) {
-    std::string s;
-    if (!token(fh, s) || s.size() != (size_t)NL * 8) return false;
-    for (int k = 0; k < NL; ++k) v[k] = (uint32_t)strtoul(s.substr((size_t)(NL - 1 - k) * 8, 8).c_str(), nullptr, 16);
-    return true;
-}
-template <int NL> static std::string hex_words(const uint32_t (&w)[NL]) {
-    std::string s;
-    char buf[9];
-    for (int k = NL - 1; k >= 0; --k) {
-        snprintf(buf, sizeof(buf), "%08x", w[k]);
-        s += buf;
-    }
-    return s;
-}
 
 template <class C> static int halo_n_case(FILE* fh, int curve) {
     using SP = typename C::SP;

@@ -7,7 +7,7 @@
 //   sigma_host_replay cases.bin out.bin
 // cases.bin: uint32 count, then per case uint32 log_n, P, M, offsets[P + 1], members[M].
 // out.bin:   per case uint32 status[3], sigma[6n], input[6n], gate[6n] (the split of sigma[w] where a value is stored, else 0xFFFFFFFF).
-// A stand-alone program: built plain and with -fsanitize=address,undefined by tests/test_sigma_host_replay.py.
+// A stand-alone program: built plain and under AddressSanitizer + UBSan by tests/test_sigma_host_replay.py.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

@@ -2,17 +2,15 @@
 curve) compiled for the host by tests/fe_sqrt_host_replay.cpp and compared with the restatement of tests/sqrt_cases.py on the whole
 case table of a 4-limb field with the deepest 2-adicity (Bls12377Scalar, 47), of the shallowest (PallasBase, 32) and of the 6-limb
 field (Bls12377Base, 46): every depth of the loop, alone and in descending runs, b = 1 at entry, the non-residue exit and a = 0, through
-the squarings and through a table indexed as SqrtRootFromTable indexes it.  The program is built a second time with
--fsanitize=address,undefined and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
-import os
-import subprocess
-
+the squarings and through a table indexed as SqrtRootFromTable indexes it.  The program is built a second time
+under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
 import pytest
 
 from oracle import bigint_ref as br
+from tests import hostprog
 from tests import sqrt_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/fe_sqrt_host_replay.cpp"
 FIELDS = (br.BLS12_377_SCALAR, br.PALLAS_BASE, br.BLS12_377_BASE)
 
 
@@ -37,17 +35,14 @@ def build_cases():
 def replayed(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("fe_sqrt")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "fe_sqrt_host_replay.cpp"), str(tmp / "cases.txt")
+    inp = str(tmp / "cases.txt")
     with open(inp, "w") as fh:
         for line, _, _ in cases:
             fh.write(line + "\n")
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.strip().split("\n")
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp)
+    lines = plain.strip().split("\n")
     assert len(lines) == len(cases)
-    return cases, lines, out.stdout, src, inp, tmp
+    return cases, lines, plain, inp, tmp
 
 
 def test_header_roots_match_the_restatement_at_every_depth(replayed):
@@ -67,9 +62,6 @@ def test_header_squarings_and_table_give_the_same_bits(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, text, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout == text, out.stdout[-2000:] + out.stderr[-2000:]
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp)
+    assert sanitized == plain

@@ -4,25 +4,22 @@ edge-value generator (src/field/field.rs:498-615) and on seeded random values.  
 exact code the GPU runs (same header, same template instantiations) before it ever reaches a GPU."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import bigint_ref as br
 from plonky_amd import synth
+from tests import hostprog
 from tests.test_oracle_kats import reference_test_inputs
 from tests.util import array_to_ints, ints_to_array
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.BLS12_377_BASE, br.PALLAS_BASE, br.VESTA_BASE]
 
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("fp") / "fp_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "fp_host_harness.cpp")])
-    L = ctypes.CDLL(so)
+    L = ctypes.CDLL(hostprog.build_shared("tests/fp_host_harness.cpp", tmp_path_factory.mktemp("fp")))
     L.fp_host_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     return L
 

@@ -5,21 +5,17 @@ build, the refusals, and the generators of a 2^10 circuit through an MSM context
 millisecond per seed); its results are cached per (curve, seed) and shared by the tests."""
 import ctypes
 import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import bigint_ref as br
 from plonky_amd import api, lib, synth
+from tests import checked_child
 from tests import hash_to_curve_ref as h2c
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 CURVES = sorted(br.CURVES)
 COUNTS = (1, 63, 64, 65, 257, 1000)         # the edges of a wave, more than one workgroup, a size that is no multiple of anything
 STARTS = (0, 5, (1 << 32) + 7)              # the last: a non-zero high word, canonical bytes above the fourth
@@ -132,14 +128,13 @@ def test_device_forms_on_a_stream_of_their_own_equal_the_host_forms():
 CHILD = r'''
 import hashlib, sys
 import numpy as np
-from plonky_amd import api, lib, synth
+from plonky_amd import api, synth
 h = hashlib.sha256()
 for curve, start, count in ((0, 0, 1), (0, 5, 65), (0, (1 << 32) + 7, 257), (0, 0, 2048), (2, 0, 257), (1, 5, 64), (3, 0, 63), (4, 0, 1000)):
     h.update(api.blake_hash_usize_to_curve(curve, start, count).tobytes())
 h.update(api.blake_hash_base_field_to_curve(2, synth.rand_field(3, 77, 200)).tobytes())
 x, y_neg = api.blake_field(3, 2, synth.rand_field(3, 78, 100))
 h.update(x.tobytes() + y_neg.tobytes())
-print("CHECKED_BUILD", lib.load().plk_checked_build())
 print("DIGEST", h.hexdigest())
 '''
 
@@ -159,21 +154,13 @@ def small_set_digest():
     return h.hexdigest()
 
 
-def run_child(**env):
-    out = subprocess.run([sys.executable, "-c", CHILD], capture_output=True, text=True, timeout=600, env=dict(os.environ, PYTHONPATH=ROOT, **env), cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    return out.stdout
-
-
 def test_the_loop_form_behind_the_knob_gives_the_same_bytes():
     """knobs are read once: the loop form runs in a process of its own"""
-    assert "DIGEST " + small_set_digest() in run_child(PLK_H2C_NAIVE="1")
+    assert "DIGEST " + small_set_digest() in checked_child.run_child(CHILD, PLK_H2C_NAIVE="1")
 
 
 def test_the_small_set_through_the_checked_build():
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    out = run_child(PLK_HIP_LIB=CHECKED)
-    assert "CHECKED_BUILD 1" in out and "DIGEST " + small_set_digest() in out
+    assert "DIGEST " + small_set_digest() in checked_child.run_checked(CHILD)
 
 
 def test_generators_of_a_circuit_commit_like_the_reference_generators():

@@ -10,10 +10,7 @@ lanes with 24 coefficients each in 4 rows of 6 (row boundaries every 1536 coeffi
 halo_b, halo_s) run one element per lane in workgroups of 256, and the generated vectors split the index at 2^10 (two-level tables).
 """
 import ctypes
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,9 +18,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import bigint_ref as br
+from tests import checked_child
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 SMALL_N = [0, 1, 2, 3, 255, 256, 257, 1000, 1 << 12, (1 << 12) + 1]
 OPEN_TILE, OPEN_ROW, LANES, LO = 6144, 1536, 256, 1024
@@ -456,23 +452,11 @@ def test_argument_errors():
     assert words_to_ints(dev.to_host(dev.powers_dev(fid, sc[0], 3))) == [mont(f, 1), mont(f, 3), mont(f, 9)]
 
 
-CHECKED_SCRIPT = r'''
-import ctypes
-from plonky_amd import lib
-L = lib.load()
-assert L.plk_checked_build() == 1, "not the checked build"
+CHECKED_BODY = '''
 from tests.test_gpu_opening import run_small_set
-compared = run_small_set()
-counts = (ctypes.c_uint * 8)()
-lib.check(L.plk_checked_failures(counts))
-print("CHECKED compared", compared, "violations", list(counts))
-assert not any(counts), list(counts)
+print("CHECKED compared", run_small_set())
 '''
 
 
 def test_checked_build_runs_the_small_set():
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    env = dict(os.environ, PLK_HIP_LIB=CHECKED, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, "-c", CHECKED_SCRIPT], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert "CHECKED compared" in out.stdout and "violations [0, 0, 0, 0, 0, 0, 0, 0]" in out.stdout
+    assert "CHECKED compared" in checked_child.run_checked(CHECKED_BODY, timeout=1200)

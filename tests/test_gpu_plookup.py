@@ -7,10 +7,7 @@ Sizes of the grand product: the row kernel's tile is LKP_ROWS x LKP_LANES = 4 x 
 exactly, 10 two tiles (the tile scan and the fix-up do work), 16 is 128 tiles - more than the 64 lanes of one wave of the tile scan, so
 its cross-wave step runs."""
 import ctypes
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,11 +17,10 @@ pytestmark = pytest.mark.gpu
 from oracle import bigint_ref as br
 from plonky_amd import api
 from plonky_amd import lib as plk
+from tests import checked_child
 from tests import plookup_ref as pr
 from tests.test_oracle_plonk import mont, unmont
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 ONE_TILE, TWO_TILES, MANY_TILES = 9, 10, 16
 
@@ -331,23 +327,11 @@ def run_small_set():
     return compared
 
 
-CHECKED_SCRIPT = r'''
-import ctypes
-from plonky_amd import lib, device as dev
-L = lib.load()
-assert L.plk_checked_build() == 1, "not the checked build"
+CHECKED_BODY = '''
 from tests.test_gpu_plookup import run_small_set
-compared = run_small_set()
-counts = (ctypes.c_uint * 8)()
-lib.check(L.plk_checked_failures(counts))
-print("CHECKED compared", compared, "violations", list(counts))
-assert not any(counts), list(counts)
+print("CHECKED compared", run_small_set())
 '''
 
 
 def test_checked_build_runs_the_small_set():
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    env = dict(os.environ, PLK_HIP_LIB=CHECKED, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, "-c", CHECKED_SCRIPT], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert "CHECKED compared 6" in out.stdout and "violations [0, 0, 0, 0, 0, 0, 0, 0]" in out.stdout
+    assert "CHECKED compared 6" in checked_child.run_checked(CHECKED_BODY)

@@ -8,10 +8,7 @@ Sizes: the count scan gives a workgroup a tile of PSORT_TILE = PSORT_LANES x PSO
 offsets' tile prefix do work), 16 is 64 tiles.  The tile scan takes PSORT_CHUNK = 256 tile sums per step, 2^18 rows: log_size 19 is
 the smallest size at which its carry between steps does work, and one case runs there."""
 import ctypes
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,12 +18,11 @@ pytestmark = pytest.mark.gpu
 from oracle import bigint_ref as br
 from plonky_amd import api
 from plonky_amd import lib as plk
+from tests import checked_child
 from tests import plookup_ref as pr
 from tests import plookup_sort_cases as sc
 from tests.test_oracle_plonk import mont, unmont
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 ONE_TILE, TWO_TILES, MANY_TILES, TWO_CHUNKS = 10, 11, 16, 19
 F0 = br.TWEEDLEDEE_BASE.field_id
@@ -259,23 +255,11 @@ def run_small_set():
     return compared
 
 
-CHECKED_SCRIPT = r'''
-import ctypes
-from plonky_amd import lib, device as dev
-L = lib.load()
-assert L.plk_checked_build() == 1, "not the checked build"
+CHECKED_BODY = '''
 from tests.test_gpu_plookup_sort import run_small_set
-compared = run_small_set()
-counts = (ctypes.c_uint * 8)()
-lib.check(L.plk_checked_failures(counts))
-print("CHECKED compared", compared, "violations", list(counts))
-assert not any(counts), list(counts)
+print("CHECKED compared", run_small_set())
 '''
 
 
 def test_checked_build_runs_the_small_set():
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    env = dict(os.environ, PLK_HIP_LIB=CHECKED, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, "-c", CHECKED_SCRIPT], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert "CHECKED compared 12" in out.stdout and "violations [0, 0, 0, 0, 0, 0, 0, 0]" in out.stdout
+    assert "CHECKED compared 12" in checked_child.run_checked(CHECKED_BODY)

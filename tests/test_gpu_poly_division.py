@@ -10,10 +10,7 @@ k' = next power of two >= k lanes per segment; the scan takes blocks of B = 64 s
 the first to need the second scan level; divisors of degree above LAZY = 8 take the step that reduces every time.
 """
 import ctypes
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,9 +18,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import bigint_ref as br
+from tests import checked_child
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 FIELDS = [br.TWEEDLEDEE_BASE, br.TWEEDLEDUM_BASE, br.BLS12_377_SCALAR, br.PALLAS_BASE, br.VESTA_BASE]
 S, B, LAZY, MAX_DEGREE = 256, 64, 8, 32
 TWO_LEVEL = S * B + 1  # the first la with more than B segments
@@ -399,24 +395,13 @@ def run_checked_case():
     return 1
 
 
-CHECKED_SCRIPT = r'''
-import ctypes
-from plonky_amd import lib, device as dev
-L = lib.load()
-assert L.plk_checked_build() == 1, "not the checked build"
+CHECKED_BODY = '''
+from plonky_amd import device as dev
 dev.init()
 from tests.test_gpu_poly_division import run_checked_case
-compared = run_checked_case()
-counts = (ctypes.c_uint * 8)()
-lib.check(L.plk_checked_failures(counts))
-print("CHECKED compared", compared, "violations", list(counts))
-assert not any(counts), list(counts)
+print("CHECKED compared", run_checked_case())
 '''
 
 
 def test_checked_build_divides():
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    env = dict(os.environ, PLK_HIP_LIB=CHECKED, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, "-c", CHECKED_SCRIPT], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert "CHECKED compared 1" in out.stdout and "violations [0, 0, 0, 0, 0, 0, 0, 0]" in out.stdout
+    assert "CHECKED compared 1" in checked_child.run_checked(CHECKED_BODY)

@@ -7,22 +7,18 @@ The Python reference is the slow side (a few milliseconds per try at 16 rounds),
 1-round context: the round loop is the permutation's own (tests/test_gpu_rescue.py), what is walked here is the tries."""
 import ctypes
 import hashlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import bigint_ref as br
 from plonky_amd import api, lib, synth
+from tests import checked_child
 from tests import rescue_h2c_ref as ref
 from tests import rescue_ref as rr
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 CURVES = sorted(br.CURVES)
 COUNTS = (1, 2, 15, 16, 17, 63, 64, 65, 257)  # a quad is a seed, a wave 16 seeds, a workgroup one wave
 DEE = api.TWEEDLEDEE
@@ -153,7 +149,7 @@ CASES = ((0, 1, 0, 1), (0, 1, 5, 65), (0, 1, 0, 1 << 11), (0, 16, 0, 17), (2, 16
 CHILD = r'''
 import hashlib
 import numpy as np
-from plonky_amd import api, lib
+from plonky_amd import api
 from tests import test_gpu_rescue_h2c as t
 h = hashlib.sha256()
 for curve, rounds, start, count in t.CASES:
@@ -161,7 +157,6 @@ for curve, rounds, start, count in t.CASES:
     h.update(api.hash_usize_to_curve(ctx, curve, start, count).tobytes())
     h.update(api.hash_base_field_to_curve(ctx, curve, t.mont_seeds(curve, range(start, start + min(count, 20)))).tobytes())
     ctx.free()
-print("CHECKED_BUILD", lib.load().plk_checked_build())
 print("DIGEST", h.hexdigest())
 '''
 
@@ -177,21 +172,13 @@ def small_set_digest():
     return h.hexdigest()
 
 
-def run_child(**env):
-    out = subprocess.run([sys.executable, "-c", CHILD], capture_output=True, text=True, timeout=600, env=dict(os.environ, PYTHONPATH=ROOT, **env), cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    return out.stdout
-
-
 def test_the_loop_form_behind_the_knob_gives_the_same_bytes(small_set_digest):
     """knobs are read once: the loop form runs in a process of its own"""
-    assert "DIGEST " + small_set_digest in run_child(PLK_H2C_NAIVE="1")
+    assert "DIGEST " + small_set_digest in checked_child.run_child(CHILD, PLK_H2C_NAIVE="1")
 
 
 def test_the_small_set_through_the_checked_build(small_set_digest):
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    out = run_child(PLK_HIP_LIB=CHECKED)
-    assert "CHECKED_BUILD 1" in out and "DIGEST " + small_set_digest in out
+    assert "DIGEST " + small_set_digest in checked_child.run_checked(CHILD)
 
 
 def test_the_points_commit_like_the_reference_points(torch_dev):

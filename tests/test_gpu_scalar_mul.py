@@ -3,9 +3,6 @@ inner-product argument's output checked by what it is for: the prover's L_j, R_j
 tampered values fail it.  Sizes are the smallest at which the kernels can go wrong (one wave per workgroup: 63 / 64 / 65, several
 workgroups: 257, 1000), not the workload's."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,12 +10,11 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import bigint_ref as br
+from tests import checked_child
 from tests import halo_endo_ref as he
 from tests import scalar_mul_cases as sc
 from tests.util import limbs_to_int
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHECKED = os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")
 ALL_CURVES = (0, 1, 2, 3, 4)
 
 
@@ -145,14 +141,10 @@ def test_scalar_mul_matches_big_integers(curve):
     sc.check(curve, prs, out, oz)
 
 
-CHECKED_SCRIPT = r'''
-import ctypes
-import numpy as np
-from plonky_amd import api, device as dev, lib
+CHECKED_BODY = '''
+from plonky_amd import api, device as dev
 from tests import scalar_mul_cases as sc
 from tests.test_gpu_scalar_mul import _all_pairs
-L = lib.load()
-assert L.plk_checked_build() == 1, "not the checked build"
 dev.init(0)
 n = 0
 for curve in (0, 1, 2, 3, 4):
@@ -161,22 +153,15 @@ for curve in (0, 1, 2, 3, 4):
     out, oz = api.curve_scalar_mul(curve, s, p, z)
     sc.check(curve, prs, out, oz)
     n += len(prs)
-counts = (ctypes.c_uint * 8)()
-lib.check(L.plk_checked_failures(counts))
-print("CHECKED cases", n, "violations", list(counts))
-assert not any(counts), list(counts)
+print("CHECKED cases", n)
 '''
 
 
 def test_scalar_mul_through_the_checked_build():
-    """The same cases through libplonky_hip_checked.so (selected through PLK_HIP_LIB in a process of its own: one HIP library per
-    process).  The kernels of scalar_mul.hip index no table - addends are selected by value from registers - so the guard counters
-    have nothing of theirs to count; they must still all be zero."""
-    assert os.path.exists(CHECKED), "libplonky_hip_checked.so is missing: python -c 'import __graft_entry__ as g; g.build()'"
-    env = dict(os.environ, PLK_HIP_LIB=CHECKED, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, "-c", CHECKED_SCRIPT], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert "CHECKED cases" in out.stdout and "violations [0, 0, 0, 0, 0, 0, 0, 0]" in out.stdout
+    """The same cases through the checked build (tests/checked_child.py: a process of its own).  The kernels of scalar_mul.hip index
+    no table - addends are selected by value from registers - so the guard counters have nothing of theirs to count; they must still
+    all be zero."""
+    assert "CHECKED cases" in checked_child.run_checked(CHECKED_BODY)
 
 
 # ---- halo_n and halo_n_mul ----

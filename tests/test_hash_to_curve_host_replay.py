@@ -1,18 +1,16 @@
 """CPU-only: plonky_amd/csrc/h2c_step.cuh (the BLAKE3 block and blake_field, the code the kernels of hash_to_curve.hip run) compiled for
 the host by tests/hash_to_curve_host_replay.cpp and compared with tests/hash_to_curve_ref.py, and both held to three published BLAKE3
-digests.  The program is built a second time with -fsanitize=address,undefined and run on its own (a stand-alone program: nothing of
+digests.  The program is built a second time under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of
 it is loaded into Python).  The reference's own points are checked against the curve equation in Python integers, and the small seed
 sets the GPU tests use are shown to reach every branch: a first try that succeeds, a third or later try, a hash that is not below the
 modulus, and both values of y_neg."""
-import os
-import subprocess
-
 import pytest
 
 from oracle import bigint_ref as br
 from tests import hash_to_curve_ref as h2c
+from tests import hostprog
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/hash_to_curve_host_replay.cpp"
 # the BLAKE3 test vectors: the hash of the empty input, bytes 32..63 of its extended output (output words 8..15: where byte BYTES of
 # every field and bytes 32..48 of Bls12377Base come from), and the hash of "abc"
 DIGEST_EMPTY = "af1349b9f5f9a1a6a0404dea36dcc9499bcb25c9adc112b7cc9a93cae41f3262"
@@ -35,15 +33,11 @@ def build_cases():
 def replayed(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("h2c")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "hash_to_curve_host_replay.cpp"), str(tmp / "cases.txt")
+    inp = str(tmp / "cases.txt")
     with open(inp, "w") as fh:
         for field, seed, it in cases:
             fh.write("%d %0*x %d\n" % (field, 16 * br.FIELDS[field].n_limbs, seed, it))
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout + out.stderr
-    return cases, out.stdout, src, inp, tmp
+    return cases, hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp), inp, tmp
 
 
 def test_python_block_reproduces_the_published_digests():
@@ -74,12 +68,9 @@ def test_header_blake_field_matches_the_reference_on_all_six_fields(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, text, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout == text, out.stdout[-2000:] + out.stderr[-2000:]
+    _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp)
+    assert sanitized == plain
 
 
 @pytest.mark.parametrize("curve", sorted(br.CURVES))

@@ -1,26 +1,22 @@
 """CPU-only: ProjectivePoint::to_affine as the library's host side computes it for the L_j / R_j of an inner-product-argument round
 (plonky_amd/csrc/hostnorm.cpp; curve.rs:206-214: x / z, y / z, zero for z = 0), against Python integers on every curve's base field."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import bigint_ref as br
+from tests import hostprog
 from tests.util import array_to_ints, ints_to_array
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # PLK_CURVE_* -> the field of its coordinates (include/plonky_hip.h)
 CURVE_BASE = [(0, br.TWEEDLEDEE_BASE), (1, br.TWEEDLEDUM_BASE), (2, br.BLS12_377_BASE), (3, br.PALLAS_BASE), (4, br.VESTA_BASE)]
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("hostnorm") / "hostnorm.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "hostnorm_harness.cpp")])
-    L = ctypes.CDLL(so)
+    L = ctypes.CDLL(hostprog.build_shared("tests/hostnorm_harness.cpp", tmp_path_factory.mktemp("hostnorm")))
     L.hostnorm_to_affine.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     return L
 

@@ -2,20 +2,17 @@
 for the host with g++ - it is plain C++ - and swept for what the kernels assume of it.  The same header, so the same arithmetic, that
 msm.hip configures every context with."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostprog
+
 TWEEDLEDEE, BLS12_377 = 0, 2
 
 
 @pytest.fixture(scope="module")
 def geom_lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("msm_geom") / "msm_geom_host.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "msm_geom_host.cpp")])
-    L = ctypes.CDLL(so)
+    L = ctypes.CDLL(hostprog.build_shared("tests/msm_geom_host.cpp", tmp_path_factory.mktemp("msm_geom")))
     L.msm_geom_check_grid.restype = ctypes.c_long
     L.msm_geom_check_grid.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_long), ctypes.c_char_p, ctypes.c_size_t]
     L.msm_geom_auto_window.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int]

@@ -6,6 +6,7 @@ import os
 import re
 
 from plonky_amd import lib
+from tests import checked_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARG_COUNTS = {
@@ -29,7 +30,7 @@ def test_opening_entries_are_declared_and_bound():
 
 def test_opening_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in ARG_COUNTS:
             assert hasattr(L, name), (so, name)

@@ -6,25 +6,19 @@ reference's own `cargo test` runs with debug assertions and overflow checks):
     tests/fp_host_sanitize_main.cpp on the host.
 A finding aborts the driver (-fno-sanitize-recover); the test asserts a clean exit and the driver's own self-checks."""
 import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-pthread",
-       "-Wall", "-Wno-unused-function"]
+from tests import hostprog
 
 
-def _build_and_run(tmp_path, src, name, marker):
-    exe = str(tmp_path / name)
-    subprocess.check_call(["g++"] + SAN + ["-o", exe, src])
+def _build_and_run(tmp_path, src, marker):
+    exe = hostprog.build(src, tmp_path, hostprog.ASAN_UBSAN, extra=("-pthread", "-Wall", "-Wno-unused-function"))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
-    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
-    assert marker in out.stdout
+    assert marker in hostprog.run(exe, timeout=900, env=env)
 
 
 def test_oracle_under_asan_ubsan(tmp_path):
-    _build_and_run(tmp_path, os.path.join(ROOT, "oracle", "sanitize_main.cpp"), "oracle_sanitize", "sanitize_main: ok")
+    _build_and_run(tmp_path, "oracle/sanitize_main.cpp", "sanitize_main: ok")
 
 
 def test_device_arithmetic_headers_under_asan_ubsan(tmp_path):
-    _build_and_run(tmp_path, os.path.join(ROOT, "tests", "fp_host_sanitize_main.cpp"), "fp_sanitize", "fp_host_sanitize: ok")
+    _build_and_run(tmp_path, "tests/fp_host_sanitize_main.cpp", "fp_host_sanitize: ok")

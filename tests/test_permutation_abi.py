@@ -5,6 +5,7 @@ import os
 import re
 
 from plonky_amd import lib
+from tests import checked_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("plk_plonk_permutation_z_dev", "plk_plonk_permutation_z")
@@ -21,7 +22,7 @@ def test_permutation_z_is_declared_and_bound():
 
 def test_permutation_z_is_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in NAMES:
             assert hasattr(L, name), (so, name)

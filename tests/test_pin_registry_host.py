@@ -2,12 +2,9 @@
 around hipHostRegister) against a model of the runtime, in tests/pin_registry_host.cpp: a stand-alone program, built plain, with
 AddressSanitizer + UBSan, and with ThreadSanitizer.  Each scenario prints the branch the registry reports for every call it makes;
 the lines are compared here, so a request that silently takes another route fails although its result may be the same."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostprog
 
 # scenario -> the branches of its calls, in order (pin_registry.h: pin_branch_name; "+waited": the request slept for another thread's
 # hold, "+recheckedN": the union path found the map changed under its synchronisation N times and looked again)
@@ -35,28 +32,17 @@ EXPECTED = {
     "stress": "balanced",
 }
 
-BUILDS = {
-    "plain": ["-O2"],
-    "asan_ubsan": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"],
-    "tsan": ["-O1", "-g", "-fsanitize=thread"],
-}
+BUILDS = {"plain": hostprog.PLAIN, "asan_ubsan": hostprog.ASAN_UBSAN, "tsan": hostprog.TSAN}
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
 def test_registry_scenarios(build, tmp_path):
-    exe = str(tmp_path / ("pin_registry_host_" + build))
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", "-Wall", "-Wextra", "-Werror"] + BUILDS[build] +
-                          ["-I" + os.path.join(ROOT, "plonky_amd", "csrc"), os.path.join(ROOT, "tests", "pin_registry_host.cpp"), "-o", exe])
-    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=300)
-    report = p.stdout[-4000:] + p.stderr[-4000:]
-    assert p.returncode == 0, report
-    for mark in ("VIOLATION", "Sanitizer", "runtime error", "WARNING:"):
-        assert mark not in p.stdout and mark not in p.stderr, report
+    out = hostprog.run(hostprog.build("tests/pin_registry_host.cpp", tmp_path, BUILDS[build], extra=hostprog.THREADS_STRICT), timeout=300)
     got = {}
-    for line in p.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("scenario "):
             name, what = line[len("scenario "):].split(": ", 1)
             assert name not in got, line
             got[name] = what
     assert got == EXPECTED
-    assert p.stdout.splitlines()[-1] == "OK"
+    assert out.splitlines()[-1] == "OK"

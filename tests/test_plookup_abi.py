@@ -12,6 +12,7 @@ import pytest
 
 from oracle import bigint_ref as br
 from plonky_amd import api, lib
+from tests import checked_child
 from tests import plookup_ref as pr
 from tests.test_oracle_plonk import mont, unmont
 
@@ -30,7 +31,7 @@ def test_entries_are_declared_and_bound_size_first():
 
 def test_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in NAMES:
             assert hasattr(L, name), (so, name)

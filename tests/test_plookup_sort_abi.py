@@ -5,6 +5,7 @@ import os
 import re
 
 from plonky_amd import api, lib
+from tests import checked_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"plk_plookup_sorted_multiset_dev": 7, "plk_plookup_sorted_multiset": 6}
@@ -21,7 +22,7 @@ def test_entries_are_declared_and_bound_size_first():
 
 def test_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in NAMES:
             assert hasattr(L, name), (so, name)

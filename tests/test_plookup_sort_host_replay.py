@@ -3,18 +3,16 @@ bisection) replayed on the host by tests/plookup_sort_host_replay.cpp in the sha
 order.  The program compares every case with a first-occurrence restatement of its own; here its s is compared with
 api.plookup_sorted_multiset, with tests/plookup_ref.sort_by at <= 64 rows and with the counting restatement, and the longest probe
 sequence of the structured tables is bounded: host and device run the same header, so this pins the hash.  The program is built a
-second time with -fsanitize=address,undefined and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
-import os
-import subprocess
-
+second time under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
 import numpy as np
 import pytest
 
 from plonky_amd import api
+from tests import hostprog
 from tests import plookup_ref as pr
 from tests import plookup_sort_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/plookup_sort_host_replay.cpp"
 SIZES = (1, 2, 6, 10)  # N = 2, 4, 64, 1024
 PROBE_BOUND = 64       # at N = 1024: 2048 slots at load 1/2; a hash that clusters the structured rows runs into the hundreds
 
@@ -45,15 +43,13 @@ def replayed(tmp_path_factory):
     """(cases, results of the plain build): the input file is shared with the sanitizer build"""
     tmp = tmp_path_factory.mktemp("plookup_sort")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "plookup_sort_host_replay.cpp"), str(tmp / "cases.bin")
+    inp = str(tmp / "cases.bin")
     with open(inp, "wb") as fh:
         fh.write(np.uint32(len(cases)).tobytes())
         for _, log_size, f, t in cases:
             fh.write(np.uint32(log_size).tobytes() + f.tobytes() + t.tobytes())
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp, str(tmp / "out.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout + out.stderr
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp, tmp / "out.bin")
+    assert "mismatches: 0" in plain, plain
     raw, results, pos = open(str(tmp / "out.bin"), "rb").read(), [], 0
     for _, log_size, _, _ in cases:
         rows = (2 << log_size) - 1
@@ -61,7 +57,7 @@ def replayed(tmp_path_factory):
         results.append((head.tolist(), np.frombuffer(raw, dtype=np.uint64, count=rows * 4, offset=pos + 12).reshape(rows, 4)))
         pos += 12 + rows * 32
     assert pos == len(raw)
-    return cases, results, src, inp, tmp
+    return cases, results, plain, inp, tmp
 
 
 def test_replay_matches_the_host_helper_and_the_reference_sort(replayed):
@@ -94,10 +90,7 @@ def test_probe_sequences_stay_short(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp, str(tmp / "out_san.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout + out.stderr
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp, tmp / "out_san.bin")
+    assert sanitized == plain
     assert open(str(tmp / "out_san.bin"), "rb").read() == open(str(tmp / "out.bin"), "rb").read()

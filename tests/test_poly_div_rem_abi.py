@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from plonky_amd import lib
+from tests import checked_child
 from tests import poly_newton_ref as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +39,7 @@ def test_entries_are_declared_and_bound_size_first():
 
 def test_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in ARG_COUNTS:
             assert hasattr(L, name), (so, name)

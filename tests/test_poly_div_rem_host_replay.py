@@ -2,16 +2,14 @@
 tests/polyinv_host_replay.cpp includes the header outside hipcc and walks, lane by lane, the seed recurrence for n = 1, 2, SEED - 1,
 SEED, one Newton level (whole, truncated, and on a reversed series: the divisor's case), whole small divisions through the
 correlation and the remainder's product, and the index maps for m = 1, 2, 3 and q_len > m.  It prints stored words; they are compared
-here with tests/poly_newton_ref.py.  The program is built and run twice: plain, and with -fsanitize=address,undefined."""
-import os
+here with tests/poly_newton_ref.py.  The program is built and run twice: plain, and under AddressSanitizer + UBSan."""
 import random
-import subprocess
 
 import pytest
 
+from tests import hostprog
 from tests import poly_newton_ref as nr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 64  # PINV_SEED
 FIELDS = {  # PLK_FIELD_* id -> modulus
     0: 0x40000000000000000000000000000000038aa127696286c9842cafd400000001,
@@ -56,16 +54,13 @@ def _cases():
     return lines, want
 
 
-@pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]], ids=["plain", "sanitized"])
-def test_steps_replayed_on_the_host(tmp_path, flags):
-    exe, script = str(tmp_path / "polyinv_host_replay"), str(tmp_path / "cases.txt")
-    subprocess.check_call(["g++", "-O1", "-std=c++17"] + flags + [os.path.join(ROOT, "tests", "polyinv_host_replay.cpp"), "-o", exe], cwd=os.path.join(ROOT, "tests"))
+@pytest.mark.parametrize("flavour", [hostprog.PLAIN, hostprog.ASAN_UBSAN], ids=["plain", "sanitized"])
+def test_steps_replayed_on_the_host(tmp_path, flavour):
+    script = str(tmp_path / "cases.txt")
     lines, want = _cases()
     with open(script, "w") as fh:
         fh.write("\n".join(lines) + "\n")
-    out = subprocess.run([exe, script], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, (out.stdout[-500:] + out.stderr[-3000:])
-    got = out.stdout.strip().split("\n")
+    got = hostprog.run(hostprog.build("tests/polyinv_host_replay.cpp", tmp_path, flavour, extra=("-Wall",)), script).strip().split("\n")
     assert len(got) == len(want)
     for line, (tag, expect) in zip(got, want):
         parts = line.split()

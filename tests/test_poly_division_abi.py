@@ -6,6 +6,7 @@ import os
 import re
 
 from plonky_amd import lib
+from tests import checked_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARG_COUNTS = {"plk_poly_division_dev": 9, "plk_poly_division": 8, "plk_poly_from_roots": 4}
@@ -34,7 +35,7 @@ def test_degree_limit_is_32():
 
 def test_division_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in ARG_COUNTS:
             assert hasattr(L, name), (so, name)

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import bigint_ref as br
 from plonky_amd import api, lib
+from tests import checked_child
 from tests import rescue_h2c_ref as ref
 from tests import rescue_ref as rr
 
@@ -37,7 +38,7 @@ def test_entries_are_declared_and_bound():
 
 def test_entries_are_exported_by_both_builds():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in DECLARATIONS:
             assert hasattr(L, name), (so, name)

@@ -1,20 +1,18 @@
 """CPU-only: plonky_amd/csrc/rescue_h2c_step.cuh (the seed formation, the y_neg bit, one try and the bounded loop over the tries - the
 code k_rescue_h2c_tries runs) compiled for the host by tests/rescue_h2c_host_replay.cpp and compared with tests/rescue_h2c_ref.py on a
 4-limb field (TweedledeeBase, under Tweedledee) and on the 6-limb field (Bls12377Base, under BLS12-377).  The program is built a
-second time with -fsanitize=address,undefined and run on its own (a stand-alone program: nothing of it is loaded into Python).
+second time under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of it is loaded into Python).
 
 The try limit is a parameter of the step, so a limit of one or two tries reaches the status-2 path that no real input reaches at 256."""
-import os
-import subprocess
-
 import pytest
 
 from oracle import bigint_ref as br
 from oracle import oracle_lib as ol
+from tests import hostprog
 from tests import rescue_h2c_ref as ref
 from tests import rescue_ref as rr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/rescue_h2c_host_replay.cpp"
 CURVES = (0, 2)  # base fields 0 (4 limbs) and 3 (6 limbs)
 ROUNDS = {0: (2, 16), 2: (2,)}
 SEEDS = list(range(12)) + [(1 << 32) - 1, 1 << 32, (1 << 64) - 1]
@@ -64,17 +62,14 @@ def replayed(tmp_path_factory):
     ol.build()
     tmp = tmp_path_factory.mktemp("rescue_h2c")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "rescue_h2c_host_replay.cpp"), str(tmp / "cases.txt")
+    inp = str(tmp / "cases.txt")
     with open(inp, "w") as fh:
         for line, _ in cases:
             fh.write(line + "\n")
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.strip().split("\n")
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp)
+    lines = plain.strip().split("\n")
     assert len(lines) == len(cases)
-    return cases, lines, out.stdout, src, inp, tmp
+    return cases, lines, plain, inp, tmp
 
 
 def _compare(replayed, kind):
@@ -107,9 +102,6 @@ def test_header_tries_match_the_restatement_and_the_limit_gives_status_two(repla
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, text, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout == text, out.stdout[-2000:] + out.stderr[-2000:]
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp)
+    assert sanitized == plain

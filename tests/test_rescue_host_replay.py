@@ -1,16 +1,14 @@
 """CPU-only: plonky_amd/csrc/rescue_step.cuh (the exponent of a k-th root, the Cauchy matrix, the windowed power chain, the row sum
 under one reduction and the round - the code the kernels of rescue.hip run) compiled for the host by tests/rescue_host_replay.cpp and
-compared with tests/rescue_ref.py on all six fields.  The program is built a second time with -fsanitize=address,undefined and run
+compared with tests/rescue_ref.py on all six fields.  The program is built a second time under AddressSanitizer + UBSan and run
 on its own (a stand-alone program: nothing of it is loaded into Python)."""
-import os
-import subprocess
-
 import pytest
 
 from oracle import bigint_ref as br
+from tests import hostprog
 from tests import rescue_ref as rr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/rescue_host_replay.cpp"
 KS = (0, 1, 2, 3, 5, 7, 11, 13, 17, 257, 65537, 1000003, 2 ** 31 - 1, 2 ** 32 - 1)
 ROUNDS = (1, 2, 10)
 
@@ -45,7 +43,7 @@ def build_cases():
 def replayed(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("rescue")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "rescue_host_replay.cpp"), str(tmp / "cases.txt")
+    inp = str(tmp / "cases.txt")
     with open(inp, "w") as fh:
         for c in cases:
             f = br.FIELDS[c[1]]
@@ -57,13 +55,10 @@ def replayed(tmp_path_factory):
                 consts = rr.constants(c[1], 4, c[2])
                 words = [hexm(f, v) for a, b in consts for v in a + b] + [hexm(f, v) for v in c[3]]
                 fh.write("P %d %d %s\n" % (c[1], c[2], " ".join(words)))
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.strip().split("\n")
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp)
+    lines = plain.strip().split("\n")
     assert len(lines) == len(cases)
-    return cases, lines, out.stdout, src, inp, tmp
+    return cases, lines, plain, inp, tmp
 
 
 def test_header_exponent_is_the_one_the_reference_walks_to(replayed):
@@ -126,9 +121,6 @@ def test_header_round_matches_the_reference_on_all_six_fields(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, text, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout == text, out.stdout[-2000:] + out.stderr[-2000:]
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp)
+    assert sanitized == plain

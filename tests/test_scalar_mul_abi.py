@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from plonky_amd import api, lib
+from tests import checked_child
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _HEAD = r"size_t\s+count\s*,\s*int\s+curve\s*,\s*"
@@ -43,7 +44,7 @@ def test_entries_are_declared_and_bound():
 
 def test_entries_are_exported_by_both_builds():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in DECLARATIONS:
             assert hasattr(L, name), (so, name)

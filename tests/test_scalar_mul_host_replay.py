@@ -1,17 +1,15 @@
 """CPU-only: plonky_amd/csrc/scalar_mul_step.cuh (the chunk decoding and n(s), the signed-digit recoding, the split along the
 endomorphism and the addend selections - the code the kernels of scalar_mul.hip run) compiled for the host by
-tests/scalar_mul_host_replay.cpp and compared with tests/halo_endo_ref.py.  The program is built a second time with
--fsanitize=address,undefined and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
-import os
-import subprocess
-
+tests/scalar_mul_host_replay.cpp and compared with tests/halo_endo_ref.py.  The program is built a second time
+under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of it is loaded into Python)."""
 import pytest
 
 from oracle import bigint_ref as br
+from tests import hostprog
 from tests import halo_endo_ref as he
 from tests import scalar_mul_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/scalar_mul_host_replay.cpp"
 GLV_BITS = 130  # glv_params.cuh
 
 
@@ -76,7 +74,7 @@ def build_cases():
 def replayed(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("scalar_mul")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "scalar_mul_host_replay.cpp"), str(tmp / "cases.txt")
+    inp = str(tmp / "cases.txt")
     with open(inp, "w") as fh:
         for c in cases:
             cv = br.CURVES[c[1]]
@@ -96,13 +94,10 @@ def replayed(tmp_path_factory):
                 fh.write("A %d %s %s\n" % (c[1], hexm(cv.base, c[2][0]), hexm(cv.base, c[2][1])))
             else:
                 fh.write("S %d %d %d %s %s\n" % (c[1], c[2], c[3], hexm(cv.base, c[4][0]), hexm(cv.base, c[4][1])))
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    lines = out.stdout.strip().split("\n")
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp)
+    lines = plain.strip().split("\n")
     assert len(lines) == len(cases)
-    return cases, lines, out.stdout, src, inp, tmp
+    return cases, lines, plain, inp, tmp
 
 
 def test_chunks_and_halo_n(replayed):
@@ -220,9 +215,6 @@ def test_chains_step_by_step(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, text, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout == text, out.stdout[-2000:] + out.stderr[-2000:]
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp)
+    assert sanitized == plain

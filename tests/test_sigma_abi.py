@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from plonky_amd import api, lib
+from tests import checked_child
 from tests import partition_ref as pref
 from tests import sigma_cases as sc
 
@@ -34,7 +35,7 @@ def test_entries_are_declared_and_bound():
 
 def test_entries_are_exported():
     lib.build()
-    for so in (lib.SO_PATH, os.path.join(ROOT, "plonky_amd", "csrc", "libplonky_hip_checked.so")):
+    for so in (lib.SO_PATH, checked_child.CHECKED):
         L = ctypes.CDLL(so)
         for name in SIGNATURES:
             assert hasattr(L, name), (so, name)

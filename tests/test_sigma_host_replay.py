@@ -1,19 +1,17 @@
 """CPU-only: the steps of the copy-constraint permutation (plonky_amd/csrc/sigma_step.cuh: bisection, neighbour rule, id split, slot
 classes, status word [0]) replayed on the host by tests/sigma_host_replay.cpp in the shape of the kernel, slots in ascending and in
 descending order.  Its sigma is compared with tests/partition_ref (the reference's to_sigma, restated) up to n = 2^10 and with the numpy
-neighbour rule at every size, its status words with their definitions, counted.  The program is built a second time with
--fsanitize=address,undefined and run on its own (a stand-alone program: nothing of it is loaded into Python); both outputs must be
+neighbour rule at every size, its status words with their definitions, counted.  The program is built a second time
+under AddressSanitizer + UBSan and run on its own (a stand-alone program: nothing of it is loaded into Python); both outputs must be
 byte-equal."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from tests import hostprog
 from tests import partition_ref as pref
 from tests import sigma_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = "tests/sigma_host_replay.cpp"
 
 
 def build_cases():
@@ -44,15 +42,13 @@ def build_cases():
 def replayed(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("sigma")
     cases = build_cases()
-    src, inp = os.path.join(ROOT, "tests", "sigma_host_replay.cpp"), str(tmp / "cases.bin")
+    inp = str(tmp / "cases.bin")
     with open(inp, "wb") as fh:
         fh.write(np.uint32(len(cases)).tobytes())
         for _, log_n, m, o, _ in cases:
             fh.write(np.array([log_n, o.shape[0] - 1, m.shape[0]], dtype=np.uint32).tobytes() + o.tobytes() + m.tobytes())
-    exe = str(tmp / "replay")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", exe], cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp, str(tmp / "out.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout + out.stderr
+    plain = hostprog.run(hostprog.build(SRC, tmp, hostprog.PLAIN, extra=("-Wall",)), inp, tmp / "out.bin")
+    assert "mismatches: 0" in plain, plain
     raw, results, pos = open(str(tmp / "out.bin"), "rb").read(), [], 0
     for _, log_n, _, _, _ in cases:
         n6 = 6 << log_n
@@ -60,7 +56,7 @@ def replayed(tmp_path_factory):
         results.append((words[:3].tolist(), words[3:3 + n6], words[3 + n6:3 + 2 * n6], words[3 + 2 * n6:]))
         pos += 4 * (3 + 3 * n6)
     assert pos == len(raw)
-    return cases, results, src, inp, tmp
+    return cases, results, plain, inp, tmp
 
 
 def test_replay_matches_the_reference_and_the_neighbour_rule(replayed):
@@ -105,10 +101,7 @@ def test_reference_refuses_what_the_status_words_count(replayed):
 
 
 def test_replay_under_the_sanitizers(replayed):
-    _, _, src, inp, tmp = replayed
-    exe = str(tmp / "replay_san")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe],
-                          cwd=os.path.join(ROOT, "tests"))
-    out = subprocess.run([exe, inp, str(tmp / "out_san.bin")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout + out.stderr
+    _, _, plain, inp, tmp = replayed
+    sanitized = hostprog.run(hostprog.build(SRC, tmp, hostprog.ASAN_UBSAN, extra=("-Wall",)), inp, tmp / "out_san.bin")
+    assert sanitized == plain
     assert open(str(tmp / "out_san.bin"), "rb").read() == open(str(tmp / "out.bin"), "rb").read()

@@ -2,12 +2,9 @@
 Plookup circuit-size tables and the tables of poly.hip) with a counting struct in place of device buffers, in
 tests/table_cache_host.cpp: a stand-alone program, built plain, with AddressSanitizer + UBSan, and with ThreadSanitizer.  Each
 scenario prints one line with what it counted; the lines are compared here."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostprog
 
 EXPECTED = {
     # a second get of a key runs no build and returns the same pointer
@@ -23,28 +20,17 @@ EXPECTED = {
     "stress": "balanced",
 }
 
-BUILDS = {
-    "plain": ["-O2"],
-    "asan_ubsan": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"],
-    "tsan": ["-O1", "-g", "-fsanitize=thread"],
-}
+BUILDS = {"plain": hostprog.PLAIN, "asan_ubsan": hostprog.ASAN_UBSAN, "tsan": hostprog.TSAN}
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
 def test_table_cache_scenarios(build, tmp_path):
-    exe = str(tmp_path / ("table_cache_host_" + build))
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", "-Wall", "-Wextra", "-Werror"] + BUILDS[build] +
-                          ["-I" + os.path.join(ROOT, "plonky_amd", "csrc"), os.path.join(ROOT, "tests", "table_cache_host.cpp"), "-o", exe])
-    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=300)
-    report = p.stdout[-4000:] + p.stderr[-4000:]
-    assert p.returncode == 0, report
-    for mark in ("VIOLATION", "Sanitizer", "runtime error", "WARNING:"):
-        assert mark not in p.stdout and mark not in p.stderr, report
+    out = hostprog.run(hostprog.build("tests/table_cache_host.cpp", tmp_path, BUILDS[build], extra=hostprog.THREADS_STRICT), timeout=300)
     got = {}
-    for line in p.stdout.splitlines():
+    for line in out.splitlines():
         if line.startswith("scenario "):
             name, what = line[len("scenario "):].split(": ", 1)
             assert name not in got, line
             got[name] = what
     assert got == EXPECTED
-    assert p.stdout.splitlines()[-1] == "OK"
+    assert out.splitlines()[-1] == "OK"
