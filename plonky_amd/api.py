@@ -599,6 +599,58 @@ def evaluate_all_constraints(field, local_constant_values, local_wire_values, ri
     return out
 
 
+WITNESS_NONE = 0xFFFFFFFF  # report words [1] and [4] when nothing failed
+
+
+class WitnessReport:
+    """What check_witness returns (include/plonky_hip_witness.h): bad_rows gate rows whose unified constraint set is not all zero,
+    first_row the smallest of them (None when there is none), first_mask its mask (bit t: term t is nonzero), first_terms (8, 4)
+    its eight terms (what evaluate_all_constraints returns for it; zeros when no row fails); bad_copies routed wires that differ from
+    their neighbour under sigma, first_copy the smallest as (input, gate) (None when there is none), sigma_out_of_range entries of
+    sigma that are not below 6n (counted, not followed); row_masks (n,) uint8 or None."""
+
+    def __init__(self, degree, report, first_terms=None, row_masks=None):
+        words = [int(w) for w in np.asarray(report).reshape(8).view(np.uint32)]
+        self.degree = degree
+        self.bad_rows = words[0]
+        self.first_row = None if words[1] == WITNESS_NONE else words[1]
+        self.first_mask = words[2]
+        self.bad_copies = words[3]
+        self.first_copy = None if words[4] == WITNESS_NONE else (words[4] // degree, words[4] % degree)
+        self.sigma_out_of_range = words[5]
+        self.first_terms = first_terms
+        self.row_masks = row_masks
+
+    @property
+    def ok(self):
+        return self.bad_rows == 0 and self.bad_copies == 0 and self.sigma_out_of_range == 0
+
+    def message(self):
+        """the reference's own words for the first failing gate (plonk.rs:158-167); None when every gate is satisfied"""
+        return None if self.first_row is None else "%d-th gate constraints are not satisfied" % self.first_row
+
+
+def check_witness(field, degree, constants, wires, sigma=None, inner_zeta=None, inner_a=None, constants_stride=1, row_masks=False):
+    """The witness check (plk_plonk_check_witness; the debug-build check of plonk.rs:158-167 without its O(n^2)): constants
+    (6, degree * constants_stride, 4) - the n-point selector columns, or constants_8n with constants_stride=8 -, wires
+    wire_values_by_wire_index (9, degree, 4), sigma (optional) the 6 degree entries of to_sigma; inner_zeta / inner_a as for
+    evaluate_all_constraints (both are needed).  Returns a WitnessReport; row_masks=True also brings back the mask of every row.
+    A witness that fails is a result: nothing is raised for it."""
+    log_degree = log2_strict(degree)
+    assert constants_stride in (1, 8), "constants_stride must be 1 or 8"
+    assert inner_zeta is not None and inner_a is not None, "inner_zeta and inner_a are needed"
+    k = _u64(constants, NUM_CONSTANTS, degree * constants_stride, 4)
+    w = _u64(wires, NUM_WIRES, degree, 4)
+    sg = _as(np.uint32, sigma, NUM_ROUTED_WIRES * degree)
+    zeta, a = _scalar(inner_zeta), _scalar(inner_a)
+    report = np.zeros(8, dtype=np.uint32)
+    masks = np.zeros(degree, dtype=np.uint8) if row_masks else None
+    terms = np.zeros((8, 4), dtype=np.uint64)
+    _call(_lib.load().plk_plonk_check_witness(log_degree, field, _ptr(k), constants_stride, _ptr(w), _ptr(sg), _ptr(zeta), _ptr(a), _ptr(report), _ptr(masks),
+                                              _ptr(terms)), refusal=True)
+    return WitnessReport(degree, report, terms, masks)
+
+
 def vanishing_points(field, degree, constants_8n, wire_values_8n, s_sigma_values_8n, plonk_z_points_8n, k_is, alpha, beta, gamma, inner_zeta, inner_a):
     """The 8n-point loop of Prover::vanishing_poly (plonk.rs:392-453); Polynomial::from_evaluations of the result
     (ifft_with_precomputation_power_of_2) is the vanishing polynomial.  Tables: (6, 8n, 4), (9, 8n, 4), (6, 8n, 4), (8n, 4)."""

@@ -613,6 +613,44 @@ int plk_plonk_evaluate_all_constraints(int field, size_t count, const uint64_t* 
     PLK_TRY(c.out(out, dout, count * 8 * 32));
     return c.finish();
 }
+// ---- the witness check (plonk.hip; include/plonky_hip_witness.h): the size comes first, the field id second ----
+int plk_plonk_check_witness_dev(unsigned log_degree, int field, const void* d_constants, unsigned constants_stride, const void* d_wires, const void* d_sigma,
+                                const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_report, void* d_row_masks, void* d_first_terms, void* stream) {
+    PLK_API;
+    return plonk_check_witness_dev_impl(log_degree, field, d_constants, constants_stride, d_wires, d_sigma, inner_zeta, inner_a, d_report, d_row_masks,
+                                        d_first_terms, as_stream(stream));
+}
+int plk_plonk_check_witness(unsigned log_degree, int field, const uint64_t* constants, unsigned constants_stride, const uint64_t* wires, const uint32_t* sigma,
+                            const uint64_t* inner_zeta, const uint64_t* inner_a, uint32_t* report, uint8_t* row_masks, uint64_t* first_terms) {
+    PLK_API;
+    PLK_TRY(plonk_check_witness_check(log_degree, field, constants, constants_stride, wires, inner_zeta, inner_a, report));
+    const size_t n = (size_t)1 << log_degree, row = n * 32;
+    // the kernel reads one constant in eight of an 8n table: gather those on the host, so that 6 n elements cross PCIe, not 6 * 8n
+    std::unique_ptr<uint64_t[]> gathered;
+    if (constants_stride == 8) {
+        gathered.reset(new (std::nothrow) uint64_t[6 * n * 4]);
+        if (!gathered) return set_error(PLK_ERR_OOM, "host buffer of %zu bytes for the constants rows", 6 * row);
+        for (size_t e = 0; e < 6 * n; ++e) memcpy(&gathered[e * 4], constants + e * 8 * 4, 32);  // row j starts at j 8n = (j n) 8
+        constants = gathered.get();
+    }
+    LaneCall c;  // after `gathered`: its destructor waits for the copies out of that buffer
+    PLK_TRY(c.begin());
+    c.pin(constants, 6 * row);
+    c.pin(wires, 9 * row);
+    c.pin(sigma, 6 * n * 4);
+    void *dc = nullptr, *dw = nullptr, *ds = nullptr, *drep = nullptr, *dmask = nullptr, *dterms = nullptr;
+    PLK_TRY(c.in(dc, constants, 6 * row));
+    PLK_TRY(c.in(dw, wires, 9 * row));
+    PLK_TRY(c.in_opt(ds, sigma, 6 * n * 4));
+    PLK_TRY(c.tmp(drep, 8 * sizeof(uint32_t)));
+    if (row_masks) PLK_TRY(c.tmp(dmask, n));
+    if (first_terms) PLK_TRY(c.tmp(dterms, 8 * 32));
+    PLK_TRY(plonk_check_witness_dev_impl(log_degree, field, dc, 1, dw, ds, inner_zeta, inner_a, drep, dmask, dterms, c.stream()));
+    PLK_TRY(c.out(report, drep, 8 * sizeof(uint32_t)));
+    if (row_masks) PLK_TRY(c.out(row_masks, dmask, n));
+    if (first_terms) PLK_TRY(c.out(first_terms, dterms, 8 * 32));
+    return c.finish();
+}
 
 // ---- the opening step: evaluations, the reduced polynomial, halo_b, halo_s, powers (opening.hip) ----
 int plk_field_powers_dev(int field, const uint64_t* x, size_t count, void* d_out, void* stream) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/plonky_hip.h"
+#include "../../include/plonky_hip_witness.h"
 #include "dispatch.cuh"
 #include "host_only.h"
 #include "table_cache.h"
@@ -265,6 +266,11 @@ int poly_div_rem_dev_impl(size_t la, int field, const void* d_a, const void* d_b
                           hipStream_t stream);
 int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_constants, const void* d_local, const void* d_right, const void* d_below,
                                    const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_out, hipStream_t stream);
+// the witness check (plonk.hip): size first, then the field id; the check holds the refusals the host entry shares
+int plonk_check_witness_check(unsigned log_degree, int field, const void* constants, unsigned constants_stride, const void* wires, const uint64_t* inner_zeta,
+                              const uint64_t* inner_a, const void* report);
+int plonk_check_witness_dev_impl(unsigned log_degree, int field, const void* d_constants, unsigned constants_stride, const void* d_wires, const void* d_sigma,
+                                 const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_report, void* d_row_masks, void* d_first_terms, hipStream_t stream);
 
 // per-vector generator ranges (and, optionally, bucket ranges) of a batched MSM execution (msm.hip: msm_execute_dev_impl; host arrays of
 // `batch` entries; scalars[b]: a device pointer)

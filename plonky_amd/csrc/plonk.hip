@@ -24,6 +24,7 @@
 #include "fp.cuh"
 #include "tables.cuh"
 #include "lz.cuh"
+#include "witness_step.cuh"
 
 namespace plk {
 
@@ -613,6 +614,178 @@ int plonk_all_constraints_dev_impl(int field, size_t count, const void* d_consta
     PlonkScalars sc;
     PLK_TRY(fill_scalars(sc, nullptr, nullptr, nullptr, nullptr, inner_zeta, inner_a));
     return or_invalid(with_field4(field, [&](auto t) { return all_constraints_t<tag_t<decltype(t)>>(count, d_constants, d_local, d_right, d_below, sc, d_out, stream); }),
+                      "field %d is not a circuit scalar field", field);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the witness check: which gate a witness does not satisfy, which routed wire differs from its copy
+// ---------------------------------------------------------------------------------------------
+// What the reference answers in debug builds only (plonk.rs:158-167: the degree-8n vanishing polynomial evaluated at each of the n
+// subgroup points, O(n^2), then "{}-th gate constraints are not satisfied").  On the subgroup the L_1 and Z terms aside, the vanishing
+// polynomial is the unified constraint set: all_constraints() above at the n rows themselves, no LDE, straight off the n-point tables
+// (or the 8n ones, one element in eight).  The copy constraints are one comparison per routed wire with its neighbour under sigma.
+//   k_check_init    the report before anything is counted
+//   k_check_rows    a lane per gate row: the eight terms SUMMED over the ten gates (TermSink - with selectors that are not 0 / 1 the
+//                   shares of two gates can cancel, so masks per gate group OR-ed together would differ from the reference), reduced to
+//                   the unique representative, bit t of the row's mask set iff term t is nonzero; count and smallest failing row by wave
+//   k_check_first   one lane evaluates the first failing row again and writes its mask and its eight terms
+//   k_check_copies  a lane per routed wire: 32 bytes at w against 32 bytes at sigma[w] (canonical elements: equal values are equal words)
+// A wave merges its lanes with a ballot (witness_step.cuh) and issues one integer atomicAdd and one atomicMin: the report does not
+// depend on the order of the waves.
+constexpr int CHECK_LANES = 128, CHECK_COPY_LANES = 256;
+
+// the unified constraint set of gate row i of the tables, in the reference's form; the row's mask.  terms (nullable): 8 elements.
+template <class P>
+PLK_DI uint32_t check_row(const uint4* __restrict__ constants, unsigned constants_stride, const uint4* __restrict__ wires, int log_degree, uint32_t i,
+                          const LzTop<P>& s_top, const uint32_t (*s_sc)[FzCfg<P>::NZ], const uint4* __restrict__ small, uint4* __restrict__ terms) {
+    using D = Lz<P, 16>;
+    const size_t n = (size_t)1 << log_degree;
+    const uint32_t i_right = witness_right(i, (unsigned)log_degree), i_below = witness_below(i, (unsigned)log_degree);
+    // constant j of row i is element (j n + i) constants_stride: stride 8 walks constants_8n, one point in eight
+    const LazyRow<P> k{constants, n * constants_stride, (size_t)i * constants_stride, s_top}, l{wires, n, i, s_top}, r{wires, n, i_right, s_top};
+    const D b2 = lz_load<P>(wires, (size_t)2 * n + i_below, s_top), b3 = lz_load<P>(wires, (size_t)3 * n + i_below, s_top);
+    Term<P> u[NUM_TERMS];
+#pragma unroll
+    for (int t = 0; t < NUM_TERMS; ++t) u[t] = Term<P>{fz_zero<P>()};
+    TermSink<P> sink{u};
+    all_constraints<P, D, GATES_ALL>(k, l, r, b2, b3, scalar_at<P>(s_sc, 9), scalar_at<P>(s_sc, 10), small, sink);
+    uint32_t mask = 0;
+#pragma unroll
+    for (int t = 0; t < NUM_TERMS; ++t) {
+        const Fe<P> c = lz_to_rform<P>(u[t].rs());  // the unique representative: zero is eight zero words
+        uint32_t any = 0;
+#pragma unroll
+        for (int w = 0; w < P::NL; ++w) any |= c.v[w];
+        if (any) mask |= 1u << t;
+        if (terms) fe_store<P>(terms + t * 2, c);
+    }
+    return mask;
+}
+
+__global__ void __launch_bounds__(64) k_check_init(uint32_t* __restrict__ report) {
+    if (threadIdx.x < WITNESS_REPORT_WORDS) report[threadIdx.x] = witness_report_init((int)threadIdx.x);
+}
+
+template <class P>
+__global__ void __launch_bounds__(CHECK_LANES) k_check_rows(const uint4* __restrict__ constants, unsigned constants_stride, const uint4* __restrict__ wires,
+                                                           const uint4* __restrict__ small, PlonkScalars sc, int log_degree, uint8_t* __restrict__ row_masks,
+                                                           uint32_t* __restrict__ report, const uint32_t* __restrict__ top_table) {
+    static_assert(P::NL == 8, "256-bit scalar fields");
+    __shared__ uint32_t s_sc[NUM_SCALARS][FzCfg<P>::NZ];
+    __shared__ __attribute__((aligned(16))) LzTop<P> s_top;
+    stage_top_table<P>(top_table, s_top);
+    stage_scalars<P>(sc, s_sc);  // ends with the barrier that publishes both
+    const uint32_t n = 1u << log_degree;
+    const uint32_t i = blockIdx.x * CHECK_LANES + threadIdx.x;  // n <= 2^27
+    uint32_t mask = 0;
+    if (i < n) {
+        mask = check_row<P>(constants, constants_stride, wires, log_degree, i, s_top, s_sc, small, nullptr);
+        if (row_masks) row_masks[i] = (uint8_t)mask;
+    }
+    // every lane of the wave is back here; the wave's lanes hold consecutive rows
+    const WitnessWave w = witness_wave_merge(__ballot(mask != 0), i - (threadIdx.x & 63));
+    if ((threadIdx.x & 63) == 0 && w.count) {
+        atomicAdd(&report[WITNESS_BAD_ROWS], w.count);
+        atomicMin(&report[WITNESS_FIRST_ROW], w.first);
+    }
+}
+
+// after k_check_rows, one workgroup: what plk_plonk_evaluate_all_constraints returns for the first failing row, zeros when there is none
+template <class P>
+__global__ void __launch_bounds__(64) k_check_first(const uint4* __restrict__ constants, unsigned constants_stride, const uint4* __restrict__ wires,
+                                                    const uint4* __restrict__ small, PlonkScalars sc, int log_degree, uint32_t* __restrict__ report,
+                                                    uint4* __restrict__ first_terms, const uint32_t* __restrict__ top_table) {
+    static_assert(P::NL == 8, "256-bit scalar fields");
+    __shared__ uint32_t s_sc[NUM_SCALARS][FzCfg<P>::NZ];
+    __shared__ __attribute__((aligned(16))) LzTop<P> s_top;
+    stage_top_table<P>(top_table, s_top);
+    stage_scalars<P>(sc, s_sc);
+    if (threadIdx.x != 0) return;
+    const uint32_t first = report[WITNESS_FIRST_ROW];
+    uint32_t mask = 0;
+    if (first < (1u << log_degree)) {
+        mask = check_row<P>(constants, constants_stride, wires, log_degree, first, s_top, s_sc, small, first_terms);
+    } else if (first_terms) {
+        const uint4 z = make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < 2 * NUM_TERMS; ++t) first_terms[t] = z;
+    }
+    report[WITNESS_FIRST_MASK] = mask;
+}
+
+// wire id w = input * n + gate is the flat index into wire_values_by_wire_index; rows 0..5 are the routed wires
+__global__ void __launch_bounds__(CHECK_COPY_LANES) k_check_copies(const uint4* __restrict__ wires, const uint32_t* __restrict__ sigma, int log_degree,
+                                                                  uint32_t* __restrict__ report) {
+    const uint32_t n6 = WITNESS_ROUTED << log_degree;
+    const uint32_t w = blockIdx.x * CHECK_COPY_LANES + threadIdx.x;  // 6n < 2^30
+    bool differs = false, out_of_range = false;
+    if (w < n6) {
+        const uint32_t s = sigma[w];
+        const WitnessCopy c = witness_copy_class(w, s, (unsigned)log_degree);
+        out_of_range = c == WITNESS_COPY_OUT_OF_RANGE;
+        if (c == WITNESS_COPY_COMPARE) {
+            const uint4 a0 = wires[(size_t)w * 2], a1 = wires[(size_t)w * 2 + 1], b0 = wires[(size_t)s * 2], b1 = wires[(size_t)s * 2 + 1];
+            differs = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+        }
+    }
+    const uint32_t base = w - (threadIdx.x & 63);
+    const WitnessWave bad = witness_wave_merge(__ballot(differs), base), far = witness_wave_merge(__ballot(out_of_range), base);
+    if ((threadIdx.x & 63) == 0) {
+        if (bad.count) {
+            atomicAdd(&report[WITNESS_BAD_COPIES], bad.count);
+            atomicMin(&report[WITNESS_FIRST_COPY], bad.first);
+        }
+        if (far.count) atomicAdd(&report[WITNESS_SIGMA_RANGE], far.count);
+    }
+}
+
+template <class P>
+static int check_witness_t(unsigned log_degree, const void* d_constants, unsigned constants_stride, const void* d_wires, const void* d_sigma, const PlonkScalars& sc,
+                           void* d_report, void* d_row_masks, void* d_first_terms, hipStream_t stream) {
+    std::shared_ptr<PlonkTables> t;
+    PLK_TRY(get_plonk_tables<P>(7, stream, t));  // the small inverses and the table of lz_from_rform: any circuit size serves
+    const uint32_t n = 1u << log_degree, n6 = WITNESS_ROUTED << log_degree;
+    k_check_init<<<1, 64, 0, stream>>>((uint32_t*)d_report);
+    k_check_rows<P><<<(n + CHECK_LANES - 1) / CHECK_LANES, CHECK_LANES, 0, stream>>>((const uint4*)d_constants, constants_stride, (const uint4*)d_wires,
+                                                                                      (const uint4*)t->small.p, sc, (int)log_degree, (uint8_t*)d_row_masks,
+                                                                                      (uint32_t*)d_report, (const uint32_t*)t->top.p);
+    k_check_first<P><<<1, 64, 0, stream>>>((const uint4*)d_constants, constants_stride, (const uint4*)d_wires, (const uint4*)t->small.p, sc, (int)log_degree,
+                                           (uint32_t*)d_report, (uint4*)d_first_terms, (const uint32_t*)t->top.p);
+    if (d_sigma)
+        k_check_copies<<<(n6 + CHECK_COPY_LANES - 1) / CHECK_COPY_LANES, CHECK_COPY_LANES, 0, stream>>>((const uint4*)d_wires, (const uint32_t*)d_sigma,
+                                                                                                         (int)log_degree, (uint32_t*)d_report);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(PLK_ERR_HIP, "witness check launch failed: %s", hipGetErrorString(e));
+    return PLK_OK;
+}
+
+// the refusals both entries share, each with its own text: nothing is launched or copied before they pass
+int plonk_check_witness_check(unsigned log_degree, int field, const void* constants, unsigned constants_stride, const void* wires, const uint64_t* inner_zeta,
+                              const uint64_t* inner_a, const void* report) {
+    const int limbs = field_limbs(field);
+    if (limbs < 0) return set_error(PLK_ERR_INVALID_ARG, "bad field id %d", field);
+    if (limbs != 4) return set_error(PLK_ERR_INVALID_ARG, "field %d has %d limbs: not a circuit scalar field", field, limbs);
+    if (log_degree > 27) return set_error(PLK_ERR_INVALID_ARG, "log_degree %u: the witness check takes log_degree <= 27", log_degree);
+    if (constants_stride != 1 && constants_stride != 8) return set_error(PLK_ERR_INVALID_ARG, "constants_stride %u is neither 1 nor 8", constants_stride);
+    if (!constants) return set_error(PLK_ERR_INVALID_ARG, "null pointer: constants");
+    if (!wires) return set_error(PLK_ERR_INVALID_ARG, "null pointer: wires");
+    if (!report) return set_error(PLK_ERR_INVALID_ARG, "null pointer: report");
+    if (!inner_zeta) return set_error(PLK_ERR_INVALID_ARG, "null pointer: inner_zeta");
+    if (!inner_a) return set_error(PLK_ERR_INVALID_ARG, "null pointer: inner_a");
+    return PLK_OK;
+}
+
+int plonk_check_witness_dev_impl(unsigned log_degree, int field, const void* d_constants, unsigned constants_stride, const void* d_wires, const void* d_sigma,
+                                 const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_report, void* d_row_masks, void* d_first_terms, hipStream_t stream) {
+    PLK_TRY(plonk_check_witness_check(log_degree, field, d_constants, constants_stride, d_wires, inner_zeta, inner_a, d_report));
+    PLK_TRY(ensure_device());
+    PlonkScalars sc;
+    PLK_TRY(fill_scalars(sc, nullptr, nullptr, nullptr, nullptr, inner_zeta, inner_a));
+    return or_invalid(with_field4(field,
+                                  [&](auto t) {
+                                      return check_witness_t<tag_t<decltype(t)>>(log_degree, d_constants, constants_stride, d_wires, d_sigma, sc, d_report, d_row_masks,
+                                                                                 d_first_terms, stream);
+                                  }),
                       "field %d is not a circuit scalar field", field);
 }
 

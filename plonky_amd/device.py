@@ -230,6 +230,33 @@ def permutation_polynomial_dev(field, log_degree, wire_values, s_sigma_values, k
     return out if status is None else (out, status)
 
 
+def check_witness_dev(field, log_degree, constants, wires, sigma=None, inner_zeta=None, inner_a=None, constants_stride=8, report=None, row_masks=None,
+                      first_terms=None):
+    """The witness check (plk_plonk_check_witness_dev, include/plonky_hip_witness.h) on device-resident tables: int64 CUDA tensors
+    constants (6, n * constants_stride, 4) - CircuitKey.constants_8n as it is with the default stride 8, the n-point columns with
+    stride 1 - and wires (9, n, 4) (wire_values_by_wire_index); sigma (optional) the (6 n,) int32 tensor of sigma_dev /
+    CircuitKey.sigma; inner_zeta / inner_a host limbs (both are needed).  Optional outputs, the caller's tensors: row_masks (n,) uint8,
+    first_terms (8, 4) int64.  Returns the report, an (8,) int32 CUDA tensor (the caller's, or a fresh one) written in stream order:
+    [0] failing rows, [1] the first (-1: none), [2] its mask, [3] routed wires that differ from their copy, [4] the first (-1: none),
+    [5] sigma entries >= 6 n, [6], [7] zero; api.WitnessReport decodes its host copy.  A witness that fails is a result, not an error."""
+    n = 1 << log_degree
+    assert constants_stride in (1, 8), "constants_stride must be 1 or 8"
+    assert inner_zeta is not None and inner_a is not None, "inner_zeta and inner_a are needed"
+    _check(constants, numel=6 * n * constants_stride * 4)
+    _check(wires, numel=9 * n * 4)
+    if sigma is not None:
+        _check(sigma, torch.int32, numel=6 * n)
+    report = _out_tensor(report, (8,), constants.device, torch.int32)
+    if row_masks is not None:
+        row_masks = _out_tensor(row_masks, (n,), constants.device, torch.uint8)
+    if first_terms is not None:
+        first_terms = _out_tensor(first_terms, (8, 4), constants.device)
+    zeta, a = _u64(inner_zeta, 4), _u64(inner_a, 4)
+    _lib.check(_lib.load().plk_plonk_check_witness_dev(log_degree, field, _dp(constants), constants_stride, _dp(wires), _dp(sigma), _hp(zeta), _hp(a), _dp(report),
+                                                       _dp(row_masks), _dp(first_terms), _stream()))
+    return report
+
+
 # ---- the copy-constraint permutation and the setup-time half of CircuitBuilder::build ----
 def sigma_dev(field, log_degree, members, offsets, k_is, want_sigma=True, status=False):
     """to_sigma (partition.rs:108-136) + sigma_polynomials (plonk_util.rs:264-280) on device-resident partitions: int32 CUDA tensors

@@ -170,6 +170,13 @@ SYMBOLS = [
     ("plk_curve_gen_bases_dev", _i, [_i, _sz, _u64, _vp, _vp, _vp, _vp]),
 ]
 
+# every symbol declared in include/plonky_hip_witness.h (a header and a table of their own: SYMBOLS mirrors include/plonky_hip.h, a pinned
+# set); the witness-check entries take the size first (_u) and the field id second, like the sigma entries
+WITNESS_SYMBOLS = [
+    ("plk_plonk_check_witness_dev", _i, [_u, _i, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_plonk_check_witness", _i, [_u, _i, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+]
+
 
 class PlonkyHipError(RuntimeError):
     def __init__(self, code, msg):
@@ -182,7 +189,7 @@ def _source_hash():
     import hashlib
     h = hashlib.sha256()
     names = sorted(f for f in os.listdir(_CSRC) if f.endswith((".hip", ".cuh", ".h", ".cpp")) or f == "Makefile")
-    for f in names + [os.path.join("..", "..", "include", "plonky_hip.h")]:
+    for f in names + [os.path.join("..", "..", "include", "plonky_hip.h"), os.path.join("..", "..", "include", "plonky_hip_witness.h")]:
         h.update(f.encode())
         with open(os.path.join(_CSRC, f), "rb") as fh:
             h.update(fh.read())
@@ -241,7 +248,7 @@ def load():
         except ImportError:
             pass
         L = ctypes.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS:
+        for name, res, args in SYMBOLS + WITNESS_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
