@@ -86,6 +86,7 @@ def check(curve, prs, out, oz):
 
 
 # ---- the split along the endomorphism, restated on integers from glv.cuh; the lattice constants are read from glv_params.cuh as data ----
+import functools
 import os
 import re
 
@@ -95,6 +96,7 @@ GLV_BITS = 130
 GLV_SHIFT = 384
 
 
+@functools.lru_cache(maxsize=None)
 def glv_params(curve):
     block = open(_GLV_FILE).read().split("struct %sGlv" % _GLV_NAMES[curve])[1].split("\n};")[0]
 

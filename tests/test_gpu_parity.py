@@ -277,11 +277,18 @@ def test_to_digits_reference_vector_on_device():
     assert list(unsigned[0]) == expected
     assert np.abs(signed).max() <= 1 << 16
     rng = np.random.default_rng(0xD161)
-    for curve, c in ((pa.TWEEDLEDEE, br.TWEEDLEDEE), (pa.TWEEDLEDUM, br.TWEEDLEDUM), (pa.BLS12_377, br.BLS12_377)):
+    from tests import glv_half_cases as gh
+    windows = (3, 5, 11, 13, 16, 17, 20, 21)
+    for curve, c in ((pa.TWEEDLEDEE, br.TWEEDLEDEE), (pa.TWEEDLEDUM, br.TWEEDLEDUM), (pa.BLS12_377, br.BLS12_377), (pa.PALLAS, br.PALLAS), (pa.VESTA, br.VESTA)):
         r = c.scalar.p
         vals = [0, 1, 2, r - 1, r - 2, (1 << 200) - 1, 1 << 200, (r - 1) // 2] + [int(v) ** 4 % r for v in rng.integers(0, 2 ** 63, 56)]
+        # the patterns of the half pools planted in k1 (every digit the tie 2^(w-1), every digit the first negative one, the carry chains):
+        # such a K < 2^126 is its own first half, so the half recoding restated in tests/glv_half_cases.py must give the device's digits
+        plants = sorted({K for w in windows + gh.WINDOWS for _, K in gh.k1_plants(curve, w)}) if curve in gh.ENDO_CURVES else []
+        first_plant = len(vals)
+        vals += plants
         sc = mont_arr(c.scalar, vals)
-        for w in (3, 5, 11, 13, 16, 17, 20, 21):
+        for w in windows:
             signed, unsigned, top_carry = pa.msm_debug_digits(curve, sc, w)
             assert not top_carry.any() and np.abs(signed).max() <= 1 << (w - 1)
             for i, v in enumerate(vals):
@@ -289,6 +296,10 @@ def test_to_digits_reference_vector_on_device():
                 ref = ol.to_digits(curve, sc[i], w)    # the reference's digit count: ceil(BITS / w)
                 got = [int(u) for u in unsigned[i]]
                 assert got[:len(ref)] == ref and not any(got[len(ref):]), (curve, w, i)
+                if i >= first_plant:
+                    half = gh.restated_half_digits(v, w)
+                    dev_digits = [int(d) for d in signed[i]]
+                    assert dev_digits[:len(half)] == half and not any(dev_digits[len(half):]), (curve, w, hex(v))
 
 
 def test_msm_tweedledee_mini_kat():
