@@ -81,16 +81,25 @@ def test_halo_whole_argument_closed_form():
 
 
 # ---- the argument behind the C ABI (plk_halo_*): device-resident vectors, frozen generators for the short rounds ----
-def _run_argument(c, n, freeze_log, seed, tabled=False, lead_rounds=0, extra_generators=0, inside=False):
+def torch_u8(flags):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(flags, dtype=np.uint8)).cuda()
+
+
+def _run_argument(c, n, freeze_log, seed, tabled=False, lead_rounds=0, extra_generators=0, inside=False, g_zero=None, inputs=None, inside_u=None):
     """All rounds through plk_halo_*; returns the per-round (L_j, R_j) and the final (a, b, g).  tabled: the first rounds run over
     the caller's commitment tables (plk_halo_begin_tabled_dev), which may hold more generators than the argument uses; inside:
-    pedersen_h and the fixed generator U are among them, u_prime = [x] U."""
+    pedersen_h and the fixed generator U are among them, u_prime = [x] U.  g_zero: (n,) identity flags of halo_g (the caller's tables
+    get them too); inputs: (g, h, up, a, b, us, blind) instead of the seeded ones; inside_u: ((2, L) words of U, x) with up = [x] U."""
     from plonky_amd import device as dev
-    g, h, up, a, b, _ = _setup(c, n, seed)
     f = c.scalar
     rounds = n.bit_length() - 1
-    us = ol.rand_field(f.field_id, seed + 50, max(rounds, 1))
-    blind = ol.rand_field(f.field_id, seed + 60, 2 * max(rounds, 1))
+    if inputs is None:
+        g, h, up, a, b, _ = _setup(c, n, seed)
+        us = ol.rand_field(f.field_id, seed + 50, max(rounds, 1))
+        blind = ol.rand_field(f.field_id, seed + 60, 2 * max(rounds, 1))
+    else:
+        g, h, up, a, b, us, blind = inputs
     tables, kw = None, {}
     if tabled:
         L = c.base.n_limbs
@@ -99,14 +108,24 @@ def _run_argument(c, n, freeze_log, seed, tabled=False, lead_rounds=0, extra_gen
         if inside:
             G = (c.gx, c.gy)
             pt = lambda P: np.array([c.base.mont_limbs(P[0]), c.base.mont_limbs(P[1])], dtype=np.uint64)
-            ubase = br.ec_mul(c, 0x2468ACE + seed, G)
-            x_int = (0x1234567 + seed) * 0x9E3779B97F4A7C15F39CC0605CEDC835 % f.p
-            up = pt(br.ec_mul(c, x_int, ubase))
-            gens += [h.reshape(1, 2, L), pt(ubase).reshape(1, 2, L)]
+            if inside_u is None:
+                ubase = br.ec_mul(c, 0x2468ACE + seed, G)
+                x_int = (0x1234567 + seed) * 0x9E3779B97F4A7C15F39CC0605CEDC835 % f.p
+                up = pt(br.ec_mul(c, x_int, ubase))
+                u_words = pt(ubase)
+            else:
+                u_words, x_int = inside_u
+            gens += [h.reshape(1, 2, L), u_words.reshape(1, 2, L)]
             kw = dict(h_index=n + extra_generators, u_index=n + extra_generators + 1, u_prime_scalar=np.array(f.mont_limbs(x_int), dtype=np.uint64))
-        tables = dev.msm_precompute_dev(c.curve_id, dev.to_device(np.concatenate(gens)))
-    arg = dev.HaloArgument(c.curve_id, dev.to_device(a), dev.to_device(b), dev.to_device(g), h, up, freeze_log=freeze_log, tables=tables,
-                           lead_rounds=lead_rounds, **kw)
+        all_gens = np.concatenate(gens)
+        tz = None
+        if g_zero is not None:
+            tz = np.zeros(all_gens.shape[0], dtype=np.uint8)
+            tz[:n] = g_zero
+            tz = torch_u8(tz)
+        tables = dev.msm_precompute_dev(c.curve_id, dev.to_device(all_gens), zero=tz)
+    arg = dev.HaloArgument(c.curve_id, dev.to_device(a), dev.to_device(b), dev.to_device(g), h, up, g_zero=None if g_zero is None else torch_u8(g_zero),
+                           freeze_log=freeze_log, tables=tables, lead_rounds=lead_rounds, **kw)
     lrs, states = [], []
     for j in range(rounds):
         lr, z = arg.round_lr(blind[2 * j], blind[2 * j + 1])
