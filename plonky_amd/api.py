@@ -1105,6 +1105,51 @@ def rescue_sponge(ctx, inputs, num_outputs):
     return out[0] if single else out
 
 
+# ---- gate witness rows (include/plonky_hip_trace.h): the blocks of the in-circuit Rescue permutation and of curve_msm ----
+TRACE_NONE = 0xFFFFFFFF  # status word [2] when no instance met an exceptional case
+
+
+def _trace_tables(n_rows, count, first_rows, wires, constants):
+    """the caller's tables as the entries take them: wires (9, n_rows, 4), fresh zeros when None; constants None (not written), True
+    (fresh zeros) or the caller's (6, n_rows, 4); first_rows (count,) uint32; four status words"""
+    assert wires is None or np.shape(wires) == (NUM_WIRES, n_rows, 4), "wires: (9, n_rows, 4)"
+    assert constants is None or constants is True or np.shape(constants) == (NUM_CONSTANTS, n_rows, 4), "constants: (6, n_rows, 4)"
+    assert np.size(first_rows) == count, "first_rows: one row per instance"
+    w = np.zeros((NUM_WIRES, n_rows, 4), dtype=np.uint64) if wires is None else _u64(wires, NUM_WIRES, n_rows, 4)
+    k = np.zeros((NUM_CONSTANTS, n_rows, 4), dtype=np.uint64) if constants is True else None if constants is None else _u64(constants, NUM_CONSTANTS, n_rows, 4)
+    return w, k, _as(np.uint32, first_rows, count), np.zeros(4, dtype=np.uint32)
+
+
+def trace_rescue_permutation(ctx, inputs, n_rows, first_rows, wires=None, constants=None):
+    """The rows CircuitBuilder::rescue_permutation lays down (circuit_builder.rs:931-970), as RescueStepAGate / RescueStepBGate generate
+    them, per instance: inputs (count, 4, 4) Montgomery limbs, first_rows (count,) the first row of each block of 2 rounds + 1 rows.
+    wires: the caller's wire_values_by_wire_index (9, n_rows, 4), written in place where it is a contiguous uint64 array (None: a
+    fresh table of zeros); constants: None, True (a fresh table) or the caller's (6, n_rows, 4) - the blocks' gate constants are then
+    written too.  Returns (wires, constants, status): status (4,) uint32, [0] blocks that would pass n_rows (not written)."""
+    a = _u64(inputs)
+    assert a.ndim == 3 and a.shape[1:] == (RESCUE_SPONGE_WIDTH, 4), "inputs: (count, 4, 4)"
+    w, k, fr, st = _trace_tables(n_rows, a.shape[0], first_rows, wires, constants)
+    _call(_lib.load().plk_trace_rescue_permutation(a.shape[0], ctx.handle, _ptr(a), n_rows, _ptr(w), _ptr(fr), _ptr(k), _ptr(st)), refusal=True)
+    return w, k, st
+
+
+def trace_curve_msm(curve, points, scalars, start, n_bits, n_rows, first_rows, wires=None, constants=None):
+    """The rows CircuitBuilder::curve_msm lays down (circuit_curve.rs:287-410) per instance: points (count, parts, 2, 4) affine points
+    of the INNER curve, scalars (count, parts, 4) elements of its base field (part.scalar.convert()), start (2, 4) the starting
+    accumulator, n_bits the bits of the chain (the builder's BITS - 1); a block is n_bits (parts + 1) rows.  Tables and result as
+    trace_rescue_permutation; status [1] counts the instances that met an exceptional case.  AssertionError where the reference
+    panics ("x_1 = x_2", "y = 0"), ValueError for a scalar with a bit at or above n_bits: the tables are written all the same."""
+    pts = _u64(points)
+    assert pts.ndim == 4 and pts.shape[2:] == (2, 4), "points: (count, parts, 2, 4)"
+    count, parts = pts.shape[:2]
+    sc = _u64(scalars)
+    assert sc.shape == (count, parts, 4), "scalars: (count, parts, 4)"
+    w, k, fr, st = _trace_tables(n_rows, count, first_rows, wires, constants)
+    _call(_lib.load().plk_trace_curve_msm(count, parts, int(n_bits), curve, _ptr(pts), _ptr(sc), _ptr(_u64(start, 2, 4)), n_rows, _ptr(w), _ptr(fr), _ptr(k),
+                                          _ptr(st)), panics=("x_1 = x_2", "y = 0"), refusal=True)
+    return w, k, st
+
+
 # ---- the Rescue hash to the curve (hash_to_curve.rs:3-11, 78-104); ctx: a RescueContext over the curve's base field ----
 def hash_base_field_to_curve(ctx, curve, seeds):
     """hash_base_field_to_curve::<C>(seed, security_bits) per row of seeds ((n, L) or (L,) Montgomery limbs of the base field), the

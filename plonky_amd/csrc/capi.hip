@@ -1370,6 +1370,92 @@ int plk_rescue_hash_field_to_curve(size_t count, const plk_rescue_ctx* ctx, int 
     return rescue_h2c_host(count, ctx, curve, seeds, 1, 0, out_xy);
 }
 
+// ---- gate witness rows (gate_trace.hip; include/plonky_hip_trace.h): count first, then the context or the shape and the curve id ----
+int plk_trace_rescue_permutation_dev(size_t count, const plk_rescue_ctx* ctx, const void* d_inputs, size_t n_rows, void* d_wires, const void* d_first_rows,
+                                     void* d_constants, void* d_status, void* stream) {
+    PLK_API;
+    return trace_rescue_dev_impl(count, ctx, d_inputs, n_rows, d_wires, d_first_rows, d_constants, d_status, as_stream(stream));
+}
+// the tables of a host-pointer trace call: up whole, written in place, down whole
+struct TraceHostTables {
+    void *dw = nullptr, *dk = nullptr, *df = nullptr, *dst = nullptr;
+    size_t row = 0;
+    int up(LaneCall& c, size_t count, size_t n_rows, uint64_t* wires, const uint32_t* first_rows, uint64_t* constants) {
+        row = n_rows * 32;
+        c.pin(wires, 9 * row);
+        c.pin(constants, 6 * row);
+        PLK_TRY(c.in(dw, wires, 9 * row));
+        PLK_TRY(c.in_opt(dk, constants, 6 * row));
+        PLK_TRY(c.in(df, first_rows, count * sizeof(uint32_t)));
+        return c.tmp(dst, 4 * sizeof(uint32_t));
+    }
+    // the status words are on the host when this returns (st: 4 words of the caller's or of this frame)
+    int down(LaneCall& c, uint64_t* wires, uint64_t* constants, uint32_t* st) {
+        PLK_TRY(c.out(wires, dw, 9 * row));
+        if (constants) PLK_TRY(c.out(constants, dk, 6 * row));
+        return c.read(st, dst, 4 * sizeof(uint32_t));
+    }
+};
+int plk_trace_rescue_permutation(size_t count, const plk_rescue_ctx* ctx, const uint64_t* inputs, size_t n_rows, uint64_t* wires, const uint32_t* first_rows,
+                                 uint64_t* constants, uint32_t* status) {
+    PLK_API;
+    PLK_TRY(trace_rescue_check(count, ctx, n_rows));
+    if (count == 0) return PLK_OK;
+    if (!inputs) return set_error(PLK_ERR_INVALID_ARG, "null pointer: inputs");
+    if (!wires) return set_error(PLK_ERR_INVALID_ARG, "null pointer: wires");
+    if (!first_rows) return set_error(PLK_ERR_INVALID_ARG, "null pointer: first_rows");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    TraceHostTables t;
+    void* di = nullptr;
+    PLK_TRY(c.in(di, inputs, count * 4 * 32));
+    PLK_TRY(t.up(c, count, n_rows, wires, first_rows, constants));
+    PLK_TRY(trace_rescue_dev_impl(count, ctx, di, n_rows, t.dw, t.df, t.dk, t.dst, c.stream()));
+    uint32_t st[4];
+    PLK_TRY(t.down(c, wires, constants, st));
+    if (status) memcpy(status, st, sizeof(st));
+    return c.finish();
+}
+int plk_trace_curve_msm_dev(size_t count, unsigned parts, unsigned n_bits, int curve, const void* d_points, const void* d_scalars, const uint64_t* start_xy,
+                            size_t n_rows, void* d_wires, const void* d_first_rows, void* d_constants, void* d_status, void* stream) {
+    PLK_API;
+    return trace_msm_dev_impl(count, parts, n_bits, curve, d_points, d_scalars, start_xy, n_rows, d_wires, d_first_rows, d_constants, d_status, as_stream(stream));
+}
+int plk_trace_curve_msm(size_t count, unsigned parts, unsigned n_bits, int curve, const uint64_t* points, const uint64_t* scalars, const uint64_t* start_xy,
+                        size_t n_rows, uint64_t* wires, const uint32_t* first_rows, uint64_t* constants, uint32_t* status) {
+    PLK_API;
+    PLK_TRY(trace_msm_check(count, parts, n_bits, curve, start_xy, n_rows));
+    if (count == 0) return PLK_OK;
+    if (!points) return set_error(PLK_ERR_INVALID_ARG, "null pointer: points");
+    if (!scalars) return set_error(PLK_ERR_INVALID_ARG, "null pointer: scalars");
+    if (!wires) return set_error(PLK_ERR_INVALID_ARG, "null pointer: wires");
+    if (!first_rows) return set_error(PLK_ERR_INVALID_ARG, "null pointer: first_rows");
+    LaneCall c;
+    PLK_TRY(c.begin());
+    TraceHostTables t;
+    void *dp = nullptr, *ds = nullptr;
+    PLK_TRY(c.in(dp, points, count * parts * 2 * 32));
+    PLK_TRY(c.in(ds, scalars, count * parts * 32));
+    PLK_TRY(t.up(c, count, n_rows, wires, first_rows, constants));
+    PLK_TRY(trace_msm_dev_impl(count, parts, n_bits, curve, dp, ds, start_xy, n_rows, t.dw, t.df, t.dk, t.dst, c.stream()));
+    uint32_t st[4];
+    PLK_TRY(t.down(c, wires, constants, st));
+    if (status) memcpy(status, st, sizeof(st));
+    if (st[1] == 0) return c.finish();
+    // which case the first such instance met, off the rows it got back: no point of these curves has x = y = 0, so its first row
+    // with wires 0 and 1 zero is where it stopped - an add row or a doubling row.  Row 0 is also where a scalar too long stops the
+    // instance: that is the case when the first addend's x is not the starting point's (equal values are equal limbs).
+    const uint32_t who = st[2], group = parts + 1;
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    const uint64_t* block = wires + (size_t)first_rows[who] * 4;
+    uint32_t k = 0;
+    while (k + 1 < n_bits * group && (memcmp(block + (size_t)k * 4, zero, 32) || memcmp(block + (n_rows + k) * 4, zero, 32))) ++k;
+    if (k == 0 && memcmp(points + (size_t)who * parts * 8, start_xy, 32))
+        return c.refuse(PLK_ERR_INVALID_ARG, "scalar bit at or above n_bits %u: instance %u (%u instances met an exceptional case)", n_bits, who, st[1]);
+    if (k % group == parts) return c.refuse(PLK_ERR_INVALID_ARG, "y = 0: instance %u, block row %u (curve_dbl.rs:157; %u instances met an exceptional case)", who, k, st[1]);
+    return c.refuse(PLK_ERR_INVALID_ARG, "x_1 = x_2: instance %u, block row %u (curve_add.rs:244; %u instances met an exceptional case)", who, k, st[1]);
+}
+
 // ---- a point times a scalar of its own, the Halo endomorphism (scalar_mul.hip): count first, curve id second ----
 int plk_curve_scalar_mul_dev(size_t count, int curve, size_t n_scalars, const void* d_scalars, size_t n_points, const void* d_p_xy, const void* d_p_zero,
                              void* d_out_xy, void* d_out_zero, void* stream) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/plonky_hip.h"
+#include "../../include/plonky_hip_trace.h"
 #include "../../include/plonky_hip_witness.h"
 #include "dispatch.cuh"
 #include "host_only.h"
@@ -271,6 +272,14 @@ int plonk_check_witness_check(unsigned log_degree, int field, const void* consta
                               const uint64_t* inner_a, const void* report);
 int plonk_check_witness_dev_impl(unsigned log_degree, int field, const void* d_constants, unsigned constants_stride, const void* d_wires, const void* d_sigma,
                                  const uint64_t* inner_zeta, const uint64_t* inner_a, void* d_report, void* d_row_masks, void* d_first_terms, hipStream_t stream);
+// gate witness rows (gate_trace.hip): count first, then the context or the shape and the curve id; the checks hold the refusals the
+// host entries share
+int trace_rescue_check(size_t count, const plk_rescue_ctx* ctx, size_t n_rows);
+int trace_rescue_dev_impl(size_t count, const plk_rescue_ctx* ctx, const void* d_inputs, size_t n_rows, void* d_wires, const void* d_first_rows,
+                          void* d_constants, void* d_status, hipStream_t stream);
+int trace_msm_check(size_t count, unsigned parts, unsigned n_bits, int curve, const uint64_t* start_xy, size_t n_rows);
+int trace_msm_dev_impl(size_t count, unsigned parts, unsigned n_bits, int curve, const void* d_points, const void* d_scalars, const uint64_t* start_xy, size_t n_rows,
+                       void* d_wires, const void* d_first_rows, void* d_constants, void* d_status, hipStream_t stream);
 
 // per-vector generator ranges (and, optionally, bucket ranges) of a batched MSM execution (msm.hip: msm_execute_dev_impl; host arrays of
 // `batch` entries; scalars[b]: a device pointer)

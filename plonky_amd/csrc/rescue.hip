@@ -152,6 +152,7 @@ int rescue_create_impl(int field, size_t width, size_t rounds, const uint64_t* c
         c->d_mds = (const uint32_t*)base;
         c->d_consts = (const uint32_t*)(base + mds_bytes);
         c->d_exp = (const uint32_t*)(base + mds_bytes + consts_bytes);
+        c->d_consts_r = base + in_off;
         hipStream_t stream = stream_pool_acquire();
         if (!stream) return (int)PLK_ERR_HIP;
         hipError_t e = hipMemcpyAsync(base + in_off, constants, in_bytes, hipMemcpyHostToDevice, stream);

@@ -14,6 +14,7 @@ struct plk_rescue_ctx {
     const uint32_t* d_mds = nullptr;
     const uint32_t* d_consts = nullptr;
     const uint32_t* d_exp = nullptr;
+    const void* d_consts_r = nullptr;  // the constants as they came (R-form): the gates' constant columns (gate_trace.hip)
 };
 
 namespace plk {

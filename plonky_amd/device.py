@@ -694,6 +694,43 @@ def kth_root_dev(field, x, k, out=None):
     return out
 
 
+# ---- gate witness rows on device-resident tables (include/plonky_hip_trace.h, gate_trace.hip) ----
+def _trace_tables_dev(n_rows, count, first_rows, wires, constants, status, device):
+    _check(first_rows, torch.int32, numel=count)
+    wires = torch.zeros((9, n_rows, 4), dtype=torch.int64, device=device) if wires is None else _out_tensor(wires, (9, n_rows, 4), device)
+    if constants is not None:
+        _check(constants, shape=(6, n_rows, 4))
+    return (wires,) + _status(status, 4, device)
+
+
+def trace_rescue_permutation_dev(ctx, inputs, n_rows, first_rows, wires=None, constants=None, status=None):
+    """The blocks of the in-circuit Rescue permutation written into a device-resident wire table: inputs (count, 4, 4) int64 CUDA
+    tensor, first_rows (count,) int32, wires (9, n_rows, 4) the prover's table, written in place (None: a fresh table of zeros),
+    constants (optional) the (6, n_rows, 4) n-point columns, whose block rows are then written too.  Asynchronous on the current
+    stream.  Returns wires; with status=True (or a (4,) int32 CUDA tensor) also the status words: [0] blocks that would pass n_rows
+    (nothing of them is written), [1] 0, [2] -1, [3] 0."""
+    _check(inputs, shape=(None, ctx.width, 4))
+    count = inputs.shape[0]
+    wires, status, sp = _trace_tables_dev(n_rows, count, first_rows, wires, constants, status, inputs.device)
+    _call(_lib.load().plk_trace_rescue_permutation_dev(count, ctx.handle, _dp(inputs), n_rows, _dp(wires), _dp(first_rows), _dp(constants), sp, _stream()),
+          refusal=True)
+    return wires if status is None else (wires, status)
+
+
+def trace_curve_msm_dev(curve, points, scalars, start, n_bits, n_rows, first_rows, wires=None, constants=None, status=None):
+    """The blocks of curve_msm written into a device-resident wire table: points (count, parts, 2, 4) and scalars (count, parts, 4)
+    int64 CUDA tensors (the INNER curve's affine points, elements of its base field), start (2, 4) host limbs, n_bits the bits of
+    the chain; tables as trace_rescue_permutation_dev.  Status words: [0] blocks that would pass n_rows, [1] instances that met an
+    exceptional case (their rows from that one on are zero), [2] the first (-1: none).  Such an instance is a result, not an error."""
+    _check(points, shape=(None, None, 2, 4))
+    count, parts = points.shape[:2]
+    _check(scalars, shape=(count, parts, 4))
+    wires, status, sp = _trace_tables_dev(n_rows, count, first_rows, wires, constants, status, points.device)
+    _call(_lib.load().plk_trace_curve_msm_dev(count, parts, int(n_bits), curve, _dp(points), _dp(scalars), _hp(_u64(start, 2, 4)), n_rows, _dp(wires),
+                                              _dp(first_rows), _dp(constants), sp, _stream()), refusal=True)
+    return wires if status is None else (wires, status)
+
+
 # ---- a point times a scalar of its own and the Halo endomorphism on device-resident tensors (scalar_mul.hip) ----
 def _scalar_mul_tensors(curve, scalars, points, zero, out, out_zero):
     L = _CURVE_LIMBS[curve]

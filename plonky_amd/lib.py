@@ -177,6 +177,15 @@ WITNESS_SYMBOLS = [
     ("plk_plonk_check_witness", _i, [_u, _i, _vp, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
+# every symbol declared in include/plonky_hip_trace.h (a header and a table of their own, as for the witness check); the gate-trace
+# entries take the count first (_sz), then the context or the shape (_u, _u) and the curve id
+TRACE_SYMBOLS = [
+    ("plk_trace_rescue_permutation_dev", _i, [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_trace_rescue_permutation", _i, [_sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("plk_trace_curve_msm_dev", _i, [_sz, _u, _u, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("plk_trace_curve_msm", _i, [_sz, _u, _u, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+]
+
 
 class PlonkyHipError(RuntimeError):
     def __init__(self, code, msg):
@@ -189,7 +198,8 @@ def _source_hash():
     import hashlib
     h = hashlib.sha256()
     names = sorted(f for f in os.listdir(_CSRC) if f.endswith((".hip", ".cuh", ".h", ".cpp")) or f == "Makefile")
-    for f in names + [os.path.join("..", "..", "include", "plonky_hip.h"), os.path.join("..", "..", "include", "plonky_hip_witness.h")]:
+    for f in names + [os.path.join("..", "..", "include", "plonky_hip.h"), os.path.join("..", "..", "include", "plonky_hip_witness.h"),
+                      os.path.join("..", "..", "include", "plonky_hip_trace.h")]:
         h.update(f.encode())
         with open(os.path.join(_CSRC, f), "rb") as fh:
             h.update(fh.read())
@@ -248,7 +258,7 @@ def load():
         except ImportError:
             pass
         L = ctypes.CDLL(SO_PATH)
-        for name, res, args in SYMBOLS + WITNESS_SYMBOLS:
+        for name, res, args in SYMBOLS + WITNESS_SYMBOLS + TRACE_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
